@@ -6,7 +6,11 @@ number, with config 2's p50 .remote() latency (gpu=1 torch.mm bf16) reported
 in the config block.
 
 Driver contract:
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K map steps and prints the result
+line. --dump-outputs DIR also writes what the last timed step returned to
+DIR/map_outputs_sorted.npy (float64). --full adds the secondary measurement
+(config 2's p50 .remote() latency probe) to the config block.
 For N>1 the driver launches this under torch.distributed.run with one rank
 per GPU. Rank 0 runs the client + in-process scheduler; every rank
 (including 0) contributes one worker pinned to its GPU. Steps are bracketed
@@ -98,6 +102,31 @@ def p50_probe_gpu(n: int) -> float:
     return float(c.float().mean().item())
 
 
+DUMP_MAX_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir: str, batches: list) -> None:
+    """Write the last timed step's map results as <out_dir>/map_outputs_sorted.npy.
+
+    The timed path consumes the map unordered (order_outputs=False), so the
+    arrival order differs run to run while the multiset of results does not:
+    the values are stored sorted, which two builds can compare element-wise.
+    Past 64 MB a fixed, seeded sample of the sorted array is kept."""
+    import numpy as np
+
+    vals = np.fromiter(
+        (float(v) for batch in batches for v in batch), dtype=np.float64
+    )
+    vals.sort()
+    max_elems = DUMP_MAX_BYTES // vals.itemsize
+    if vals.size > max_elems:
+        keep = np.random.default_rng(0).choice(vals.size, size=max_elems, replace=False)
+        keep.sort()
+        vals = vals[keep]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "map_outputs_sorted.npy"), vals)
+
+
 def run_worker_rank(rank: int, world: int) -> None:
     """Ranks > 0: host one worker connected to rank 0's scheduler, plus
     participate in the start/end barriers from the main thread."""
@@ -165,6 +194,14 @@ def main() -> None:
     parser.add_argument("--steps", type=int, default=8)
     parser.add_argument("--warmup", type=int, default=2)
     parser.add_argument("--items-per-gpu", type=int, default=ITEMS_PER_GPU)
+    parser.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="write the last timed step's map results to DIR/map_outputs_sorted.npy",
+    )
+    parser.add_argument(
+        "--full", action="store_true",
+        help="also run the secondary measurements (config-2 p50 .remote() probe)",
+    )
     args = parser.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -254,14 +291,18 @@ def main() -> None:
         item_fn = app.function(gpu=1 if has_gpu else None)(
             modal.concurrent(max_inputs=8)(work_fn)
         )
-    probe_fn = app.function(gpu=1 if has_gpu else None)(p50_probe_gpu) if has_gpu else None
+    probe_fn = None
+    if args.full and has_gpu:
+        probe_fn = app.function(gpu=1)(p50_probe_gpu)
 
     items_per_step = args.items_per_gpu * n_gpus
 
-    def run_map_step() -> None:
+    def run_map_step(keep: list | None = None) -> None:
         """One map step driven on the framework loop (no per-item sync
         bridge); batch-wise consumption (map_batches) skips the per-item
-        flatten — every item is still produced and counted."""
+        flatten — every item is still produced and counted. `keep`
+        collects the result batches (the last timed step, for
+        --dump-outputs)."""
 
         async def _consume() -> None:
             n = 0
@@ -269,6 +310,8 @@ def main() -> None:
                 range(items_per_step), order_outputs=False
             ):
                 n += len(batch)
+                if keep is not None:
+                    keep.append(batch)
             assert n == items_per_step
 
         synchronizer.run(_consume())
@@ -276,7 +319,7 @@ def main() -> None:
     ctx = app.run(client=client)
     ctx.__enter__()
     try:
-        # ---- warmup: also measures config-2 p50 .remote() latency ------
+        # ---- warmup (--full: also measures config-2 p50 .remote() latency)
         p50_ms = None
         if probe_fn is not None:
             lat = []
@@ -296,8 +339,9 @@ def main() -> None:
         if has_gpu:
             torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            run_map_step()
+        last_batches: list | None = [] if args.dump_outputs else None
+        for step in range(args.steps):
+            run_map_step(last_batches if step == args.steps - 1 else None)
         if dist is not None:
             dist.barrier()
         if has_gpu:
@@ -307,6 +351,9 @@ def main() -> None:
             t = torch.tensor([elapsed], dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_batches)
 
         total_items = args.steps * items_per_step
         result = {

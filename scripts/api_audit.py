@@ -4,18 +4,27 @@ For each mapped (reference file, class) -> (our module, class), list public
 methods/properties the reference exposes that we don't. Names in ALLOW are
 accepted gaps (documented in docs/PARITY.md). Run: python scripts/api_audit.py
 Exit code 1 if any unexplained gap exists (used by tests).
+
+The reference's public member names are recorded in
+tests/golden/ref_api_members.json, so the audit needs no reference checkout.
+`python scripts/api_audit.py --ref <reference>/py/modal` re-parses a reference
+tree instead, and with `--record` rewrites the recorded list from it.
 """
 
 from __future__ import annotations
 
+import argparse
 import ast
 import importlib
+import json
 import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 
-REF = "/root/reference/py/modal"
+GOLDEN = os.path.join(
+    os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden", "ref_api_members.json"
+)
 
 # (ref_file, ref_class) -> (our_module, our_class)
 MAP = [
@@ -48,8 +57,8 @@ ALLOW = {
 }
 
 
-def ref_members(path: str, klass: str) -> set[str]:
-    tree = ast.parse(open(f"{REF}/{path}").read())
+def ref_members(ref: str, path: str, klass: str) -> set[str]:
+    tree = ast.parse(open(f"{ref}/{path}").read())
     for node in ast.walk(tree):
         if isinstance(node, ast.ClassDef) and node.name == klass:
             out = set()
@@ -68,9 +77,27 @@ def our_members(module: str, klass: str) -> set[str]:
 
 
 def main() -> int:
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--ref", default=None, help="parse this reference py/modal tree")
+    parser.add_argument("--record", action="store_true", help="rewrite the recorded names from --ref")
+    args = parser.parse_args()
+    if args.record and not args.ref:
+        parser.error("--record needs --ref")
+    if args.ref:
+        recorded = {
+            f"{ref_file}::{ref_cls}": sorted(ref_members(args.ref, ref_file, ref_cls))
+            for ref_file, ref_cls, _, _ in MAP
+        }
+        if args.record:
+            with open(GOLDEN, "w") as f:
+                json.dump(recorded, f, indent=1, sort_keys=True)
+                f.write("\n")
+    else:
+        with open(GOLDEN) as f:
+            recorded = json.load(f)
     bad = 0
     for ref_file, ref_cls, our_mod, our_cls in MAP:
-        want = ref_members(ref_file, ref_cls)
+        want = set(recorded[f"{ref_file}::{ref_cls}"])
         have = our_members(our_mod, our_cls)
         missing = sorted(want - have - ALLOW.get(our_cls, set()) - ALLOW.get(ref_cls, set()))
         if missing:

@@ -40,11 +40,11 @@ def test_pack_payloads_roundtrip():
     assert core.unpack_payloads(blob) == items
 
 
-def test_attach_to_daemon_scheduler(tmp_path):
+def test_attach_to_daemon_scheduler(run_dir):
     """A second process's scheduler serves this client over the socket
     (the cross-process wire contract: app create, function create, map,
     queue ops)."""
-    run_dir = str(tmp_path / "daemon")
+    run_dir = os.path.join(run_dir, "daemon")  # short: AF_UNIX paths cap at 108 bytes
     daemon = subprocess.Popen(
         [sys.executable, "-m", "modal_amd.cli.entry_point", "daemon", "--run-dir", run_dir],
         stdout=subprocess.PIPE,

@@ -77,10 +77,11 @@ def test_flash_manager_registry():
     assert mgr.list() == []
 
 
-def test_import_telemetry_socket(tmp_path):
+def test_import_telemetry_socket(run_dir):
     from modal_amd.runtime.telemetry import instrument_imports, uninstrument_imports
 
-    sock_path = str(tmp_path / "telemetry.sock")
+    # short mkdtemp dir: AF_UNIX paths cap at 108 bytes, pytest's tmp_path may not fit
+    sock_path = os.path.join(run_dir, "telemetry.sock")
     received = []
     server = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     server.bind(sock_path)

@@ -25,18 +25,34 @@ def _check_result(line: str, n_gpus: int) -> None:
     assert result["scaling"] == "weak"
     assert result["data"] == "synthetic"
     assert result["config"]["global_batch"] > 0
+    assert result["steps"] >= 1 and result["ms_per_step"] > 0
+    # ms_per_step is the time of ONE timed step, consistent with the headline
+    items = result["steps"] * result["config"]["global_batch"]
+    assert result["value"] == pytest.approx(
+        items / (result["steps"] * result["ms_per_step"] / 1000.0), rel=1e-6
+    )
 
 
 def test_bench_single_process(tmp_path):
     proc = subprocess.run(
         [sys.executable, "bench.py", "--gpus", "1", "--steps", "1",
-         "--warmup", "0", "--items-per-gpu", "64"],
+         "--warmup", "0", "--items-per-gpu", "64",
+         "--dump-outputs", str(tmp_path / "out")],
         cwd=REPO, capture_output=True, text=True, timeout=180,
         env={**os.environ, "MASTER_PORT": "0"},
     )
     assert proc.returncode == 0, proc.stderr[-2000:]
     line = [ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1]
     _check_result(line, 1)
+    # a plain run skips the secondary p50 probe (it lives behind --full)
+    assert json.loads(line)["config"]["p50_remote_ms"] is None
+    # --dump-outputs: the last timed step's results, sorted (the CPU payload
+    # is the identity, so exactly 0..63)
+    import numpy as np
+
+    out = np.load(tmp_path / "out" / "map_outputs_sorted.npy")
+    assert out.dtype == np.float64
+    assert out.tolist() == [float(x) for x in range(64)]
 
 
 @pytest.mark.timeout(240)

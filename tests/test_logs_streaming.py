@@ -50,10 +50,10 @@ def test_app_get_logs_offset_resume(client):
         assert resp["entries"] == []
 
 
-def test_daemon_attached_tail_live(tmp_path):
+def test_daemon_attached_tail_live(run_dir):
     """`modal-amd app logs -f` against a daemon-hosted app: the tail sees
     lines produced AFTER it started (live, not a snapshot)."""
-    run_dir = str(tmp_path / "daemon")
+    run_dir = os.path.join(run_dir, "daemon")  # short: AF_UNIX paths cap at 108 bytes
     daemon = subprocess.Popen(
         [sys.executable, "-m", "modal_amd.cli.entry_point", "daemon", "--run-dir", run_dir],
         stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True,
@@ -113,11 +113,11 @@ print("TAIL_OK")
             daemon.kill()
 
 
-def test_daemon_attached_app_run_streams_logs(tmp_path):
+def test_daemon_attached_app_run_streams_logs(run_dir):
     """app.run() with enable_output against a DAEMON scheduler streams the
     app's worker prints back to the attached terminal (round-1: the proxy
     path returned nothing)."""
-    run_dir = str(tmp_path / "daemon")
+    run_dir = os.path.join(run_dir, "daemon")  # short: AF_UNIX paths cap at 108 bytes
     daemon = subprocess.Popen(
         [sys.executable, "-m", "modal_amd.cli.entry_point", "daemon", "--run-dir", run_dir],
         stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True,

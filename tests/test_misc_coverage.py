@@ -513,10 +513,11 @@ def test_volume_mount_options(client, tmp_path):
 
     scoped = v.with_mount_options(sub_path="sub")
     app = modal.App("vol-opts")
+    mount = str(tmp_path / "data")  # writable without root
 
-    @app.function(volumes={"/data": scoped})
+    @app.function(volumes={mount: scoped})
     def peek():
-        with open("/data/inner.txt") as f:
+        with open(mount + "/inner.txt") as f:
             return f.read()
 
     with app.run(client=client):

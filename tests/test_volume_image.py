@@ -60,14 +60,16 @@ def test_volume_named_persistence(client):
         modal.Volume.from_name("train-data").hydrate()
 
 
-def test_volume_in_worker_function(client):
+def test_volume_in_worker_function(client, tmp_path):
     """Functions see mounted volumes via the shared tree (config 4 path)."""
     app = modal.App("vol-app")
     vol = modal.Volume.from_name("fn-vol", create_if_missing=True)
+    # mount under tmp_path: an unprivileged user cannot create /data-vol
+    mount = str(tmp_path / "data-vol")
 
-    @app.function(volumes={"/data-vol": vol})
+    @app.function(volumes={mount: vol})
     def writer(text):
-        with open("/data-vol/out.txt", "w") as f:
+        with open(mount + "/out.txt", "w") as f:
             f.write(text)
         return "written"
 
@@ -147,14 +149,15 @@ def test_image_run_function_failure_surfaces(client):
         img.hydrate()
 
 
-def test_exit_hook_writes_land_before_volume_commit(client):
+def test_exit_hook_writes_land_before_volume_commit(client, tmp_path):
     """@exit hooks run before the exit-time volume commit (parity:
     lifecycle finalization then task_lifecycle_manager.py:117-120), so
     files written in @exit are visible in the committed volume."""
     app = modal.App("exit-vol-app")
     vol = modal.Volume.from_name("exit-vol", create_if_missing=True)
+    mount = str(tmp_path / "exit-vol")  # writable without root
 
-    @app.cls(volumes={"/exit-vol": vol})
+    @app.cls(volumes={mount: vol})
     class Svc:
         @modal.enter()
         def up(self):
@@ -167,7 +170,7 @@ def test_exit_hook_writes_land_before_volume_commit(client):
 
         @modal.exit()
         def down(self):
-            with open("/exit-vol/final.txt", "w") as f:
+            with open(mount + "/final.txt", "w") as f:
                 f.write(f"count={self.n}")
 
     with app.run(client=client):
