@@ -58,6 +58,18 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                 ctypes.c_long, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
             ]
+            lib.ma_malz_plan.restype = ctypes.c_int
+            lib.ma_malz_plan.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_void_p]
+            lib.ma_malz_assemble.restype = ctypes.c_int
+            lib.ma_malz_assemble.argtypes = (
+                [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 6
+                + [ctypes.c_int, ctypes.c_void_p]
+            )
+            lib.ma_malz_copy.restype = ctypes.c_int
+            lib.ma_malz_copy.argtypes = [
+                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_int,
+                ctypes.c_void_p,
+            ]
             from .rawmem import _bind as _bind_rawmem
 
             _bind_rawmem(lib)

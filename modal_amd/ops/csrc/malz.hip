@@ -1,0 +1,212 @@
+// MALZ41 container assembly on the device for gfx950 (MI355X, CDNA4).
+//
+// The LZ4 kernel (lz4.hip) leaves every 4 KiB segment's block in a fixed-
+// stride slot plus a comp_len per segment. Finishing the container (layout in
+// ops/compress.py) used to mean reading the whole strided buffer back and
+// compacting on the host. These two kernels do it where the data lives, for a
+// batch of blocks at once, so the only large D2H is the dense container:
+//
+//   plan      per block: eff[i] = comp_len ? comp_len : raw segment length,
+//             exclusive scan -> seg_off, sum -> blk_payload (the host's
+//             keep/raw decision needs only that one int64 per block)
+//   assemble  per kept block: header + comp_len table + every segment's
+//             bytes at 18 + 4*n_seg + seg_off[s], compressed segments from
+//             their stride slot, raw ones from the source
+//
+// Segment arrays (comp_lens, seg_off, stride slots) are indexed by
+// blk_first_seg[b] + s; a block's segment count is ceil(blk_raw_len[b]/4096).
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define SEG_SIZE 4096
+#define PLAN_BLOCK 256
+#define WAVE 64
+#define ASM_BLOCK 256
+#define ASM_WAVES (ASM_BLOCK / WAVE)  // one wavefront per segment
+#define ASM_GROUPS 512                // x 4 waves = the 2048 segments of 8 MiB
+#define HEADER_FIXED 18               // magic(6) + u64 raw_len + u32 n_seg
+#define MAX_GRID_Y 65535
+
+__device__ __forceinline__ int seg_eff(int clen, int64_t raw_len, int64_t s) {
+  if (clen) return clen;
+  int64_t left = raw_len - s * SEG_SIZE;
+  return (int)(left < SEG_SIZE ? left : SEG_SIZE);
+}
+
+extern "C" __global__ __launch_bounds__(PLAN_BLOCK) void malz_plan_kernel(
+    const int32_t* __restrict__ comp_lens,
+    const int32_t* __restrict__ blk_first_seg,
+    const int64_t* __restrict__ blk_raw_len,
+    int32_t* __restrict__ seg_off,
+    int64_t* __restrict__ blk_payload) {
+  __shared__ int64_t wave_sum[PLAN_BLOCK / WAVE];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wave = tid / WAVE;
+  const int64_t raw_len = blk_raw_len[b];
+  const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
+  const int32_t* cl = comp_lens + blk_first_seg[b];
+  int32_t* so = seg_off + blk_first_seg[b];
+
+  // each thread owns a run of consecutive segments (8 for an 8 MiB block)
+  const int64_t per = (n_seg + PLAN_BLOCK - 1) / PLAN_BLOCK;
+  const int64_t lo = min((int64_t)tid * per, n_seg);
+  const int64_t hi = min(lo + per, n_seg);
+  int64_t mine = 0;
+  for (int64_t s = lo; s < hi; ++s) mine += seg_eff(cl[s], raw_len, s);
+
+  // inclusive scan inside the wave, then across the 4 waves through LDS
+  int64_t incl = mine;
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    int64_t up = __shfl_up(incl, d, WAVE);
+    if (lane >= d) incl += up;
+  }
+  if (lane == WAVE - 1) wave_sum[wave] = incl;
+  __syncthreads();
+  int64_t base = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < PLAN_BLOCK / WAVE; ++w) {
+    if (w < wave) base += wave_sum[w];
+    total += wave_sum[w];
+  }
+  int64_t run = base + incl - mine;
+  for (int64_t s = lo; s < hi; ++s) {
+    so[s] = (int32_t)run;
+    run += seg_eff(cl[s], raw_len, s);
+  }
+  if (tid == 0) blk_payload[b] = total;
+}
+
+// Copy len bytes with one wavefront, byte-exact for any src/dst alignment:
+// byte lanes up to dst's 16-byte boundary, dwordx4 stores on the body fed by
+// aligned loads (dwordx4 when src is co-aligned, else five dwords funnelled
+// to the byte shift), byte lanes on the tail.
+__device__ void wave_copy(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                          int len, int lane) {
+  int head = (int)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15);
+  if (head > len) head = len;
+  if (lane < head) dst[lane] = src[lane];
+  src += head; dst += head; len -= head;
+
+  const int n_vec = len >> 4;
+  uint4* d4 = reinterpret_cast<uint4*>(dst);
+  const int mis = (int)(reinterpret_cast<uintptr_t>(src) & 3);
+  if ((reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+    const uint4* s4 = reinterpret_cast<const uint4*>(src);
+    for (int k = lane; k < n_vec; k += WAVE) d4[k] = s4[k];
+  } else if (mis == 0) {
+    const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src);
+    for (int k = lane; k < n_vec; k += WAVE) {
+      uint4 v;
+      v.x = s1[4 * k + 0]; v.y = s1[4 * k + 1];
+      v.z = s1[4 * k + 2]; v.w = s1[4 * k + 3];
+      d4[k] = v;
+    }
+  } else {
+    // the five aligned dwords that cover src[16k .. 16k+15]; the first and
+    // the last each hold at least one of those bytes, so no load leaves the
+    // dwords the copy's own source bytes live in
+    const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src - mis);
+    const int sh = mis * 8;
+    for (int k = lane; k < n_vec; k += WAVE) {
+      uint32_t w0 = s1[4 * k + 0], w1 = s1[4 * k + 1], w2 = s1[4 * k + 2];
+      uint32_t w3 = s1[4 * k + 3], w4 = s1[4 * k + 4];
+      uint4 v;
+      v.x = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
+      v.y = (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh);
+      v.z = (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh);
+      v.w = (uint32_t)((((uint64_t)w4 << 32) | w3) >> sh);
+      d4[k] = v;
+    }
+  }
+  const int tail_start = n_vec << 4;
+  if (lane < len - tail_start) dst[tail_start + lane] = src[tail_start + lane];
+}
+
+__device__ __forceinline__ void put_le(uint8_t* dst, uint64_t v, int nbytes, int lane) {
+  if (lane < nbytes) dst[lane] = (uint8_t)(v >> (8 * lane));
+}
+
+extern "C" __global__ __launch_bounds__(ASM_BLOCK) void malz_assemble_kernel(
+    const uint8_t* __restrict__ src,
+    const int64_t* __restrict__ blk_src_off,
+    const uint8_t* __restrict__ stride_buf, int out_stride,
+    const int32_t* __restrict__ comp_lens,
+    const int32_t* __restrict__ seg_off,
+    const int32_t* __restrict__ blk_first_seg,
+    const int64_t* __restrict__ blk_raw_len,
+    uint8_t* __restrict__ out,
+    const int64_t* __restrict__ blk_out_off,
+    int blk_base) {
+  const int b = blk_base + blockIdx.y;
+  const int64_t out_off = blk_out_off[b];
+  if (out_off < 0) return;  // block stored raw: nothing to assemble
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int64_t raw_len = blk_raw_len[b];
+  const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
+  const int64_t first = blk_first_seg[b];
+  uint8_t* blk_out = out + out_off;
+
+  if (blockIdx.x == 0 && wave == 0) {
+    const uint64_t magic = 0x31345A4C414DULL;  // "MALZ41", little-endian
+    put_le(blk_out, magic, 6, lane);
+    put_le(blk_out + 6, (uint64_t)raw_len, 8, lane);
+    put_le(blk_out + 14, (uint64_t)n_seg, 4, lane);
+  }
+  uint8_t* table = blk_out + HEADER_FIXED;
+  uint8_t* payload = table + 4 * n_seg;
+  const uint8_t* blk_src = src + blk_src_off[b];
+  for (int64_t s = (int64_t)blockIdx.x * ASM_WAVES + wave; s < n_seg;
+       s += (int64_t)gridDim.x * ASM_WAVES) {
+    const int clen = comp_lens[first + s];
+    put_le(table + 4 * s, (uint32_t)clen, 4, lane);
+    const uint8_t* from = clen ? stride_buf + (first + s) * out_stride
+                               : blk_src + s * SEG_SIZE;
+    wave_copy(from, payload + seg_off[first + s], seg_eff(clen, raw_len, s), lane);
+  }
+}
+
+extern "C" int ma_malz_plan(const void* comp_lens, const void* blk_first_seg,
+                            const void* blk_raw_len, void* seg_off, void* blk_payload,
+                            int n_blocks, void* stream) {
+  if (n_blocks <= 0) return 0;
+  hipLaunchKernelGGL(malz_plan_kernel, dim3(n_blocks), dim3(PLAN_BLOCK), 0,
+                     (hipStream_t)stream, (const int32_t*)comp_lens,
+                     (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
+                     (int32_t*)seg_off, (int64_t*)blk_payload);
+  return (int)hipGetLastError();
+}
+
+extern "C" int ma_malz_assemble(const void* src, const void* blk_src_off,
+                                const void* stride_buf, int out_stride,
+                                const void* comp_lens, const void* seg_off,
+                                const void* blk_first_seg, const void* blk_raw_len,
+                                void* out, const void* blk_out_off, int n_blocks,
+                                void* stream) {
+  for (int base = 0; base < n_blocks; base += MAX_GRID_Y) {
+    int ny = n_blocks - base < MAX_GRID_Y ? n_blocks - base : MAX_GRID_Y;
+    hipLaunchKernelGGL(malz_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
+                       (hipStream_t)stream, (const uint8_t*)src,
+                       (const int64_t*)blk_src_off, (const uint8_t*)stride_buf, out_stride,
+                       (const int32_t*)comp_lens, (const int32_t*)seg_off,
+                       (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
+                       (uint8_t*)out, (const int64_t*)blk_out_off, base);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return (int)err;
+  }
+  return 0;
+}
+
+// Async copy on the caller's stream for the raw-pointer codec (ops/devcodec.py):
+// kind 1 = host->device, 2 = device->host.
+extern "C" int ma_malz_copy(void* dst, const void* src, unsigned long long nbytes,
+                            int kind, void* stream) {
+  if (nbytes == 0) return 0;
+  return (int)hipMemcpyAsync(dst, src, nbytes,
+                             kind == 1 ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost,
+                             (hipStream_t)stream);
+}

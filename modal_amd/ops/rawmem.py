@@ -112,6 +112,21 @@ def restore_all(saved: dict[str, bytes]) -> None:
             raise RuntimeError(f"restore write {key} -> hipError {rc}")
 
 
+def acquire(key: str, size: int) -> int:
+    """Device pointer of the tracked buffer ``key``: re-acquired when the
+    registry has the key (after release_all), freshly allocated otherwise."""
+    lib = load_lib(required=True)
+    ptr = ctypes.c_void_p()
+    kb = key.encode()
+    if key in _iter_keys(lib):
+        rc = lib.ma_tracked_reacquire(kb, ctypes.byref(ptr))
+    else:
+        rc = lib.ma_tracked_alloc(kb, ctypes.c_ulonglong(size), ctypes.byref(ptr))
+    if rc != 0:
+        raise RuntimeError(f"restore alloc {key} -> hipError {rc}")
+    return ptr.value or 0
+
+
 def lookup(key: str) -> Optional[tuple[int, int]]:
     """(device_ptr, size) of a tracked buffer, or None."""
     lib = load_lib()

@@ -20,6 +20,12 @@ $MODAL_AMD_RESTORE_STATE_PATH, defaulting to the reference's
 ``/__modal/restore-state.json``), applies env overrides, loads the snapshot
 payload, and exits with the sentinel code 222 on failure so the supervisor
 retries without snapshot.
+
+Two payload versions restore through ``restore_payload``: version 1
+(``capture_payload``) carries every byte inline in one pickle; version 2
+(``capture_manifest``, opt-in) stores the state as content-addressed blocks
+in a ``BlobStore``, encoded on the GPU for device memory (ops/devcodec.py),
+and carries only their digests.
 """
 
 from __future__ import annotations
@@ -258,10 +264,18 @@ def capture_payload() -> bytes:
     return pickle.dumps(payload, 4)
 
 
-def restore_payload(data: bytes) -> dict:
-    """Rehydrate a capture_payload() blob into THIS process. Returns the
-    fidelity report recorded at capture time."""
+def restore_payload(data: bytes, store: Any = None) -> dict:
+    """Rehydrate a capture_payload() or capture_manifest() blob into THIS
+    process. A version-2 manifest names CAS blocks, so it needs the
+    ``BlobStore`` that holds them. Returns the fidelity report recorded at
+    capture time."""
     payload = pickle.loads(data)
+    if payload.get("version") == 2:
+        if store is None:
+            raise ValueError("a version-2 snapshot manifest needs the blob store of its blocks")
+        _restore_manifest(payload, store)
+        _rng_restore(payload.get("rng", {}))
+        return payload.get("fidelity", {})
     from ..ops import rawmem
 
     if payload.get("raw"):
@@ -285,6 +299,143 @@ def restore_payload(data: bytes) -> dict:
             raise
     _rng_restore(payload.get("rng", {}))
     return payload.get("fidelity", {})
+
+
+# ---------------------------------------------------------------------------
+# version 2: block-addressed manifests (payload lives in the CAS)
+# ---------------------------------------------------------------------------
+
+#: blocks fetched and decoded per call on restore (bounds host memory)
+_RESTORE_CHUNK_BLOCKS = 8
+
+
+def capture_manifest(store: Any) -> bytes:
+    """Block-addressed snapshot: every registered tensor and tracked raw
+    allocation is cut into CAS blocks, hashed and compressed where it lives
+    (CUDA memory on the GPU through ops/devcodec.py, CPU tensors on the
+    host), each new block goes to ``store`` and only the digests are
+    returned. Blocks the store already has are neither compressed nor
+    copied, so a second snapshot of unchanged state costs its hashing."""
+    from ..ops import devcodec, rawmem
+
+    def entry_for(nbytes: int, **extra: Any) -> dict:
+        return {"blocks": [], "block_lens": [], "nbytes": nbytes, **extra}
+
+    def add(entry: dict, blk: Any) -> None:
+        if blk.payload is not None:
+            store.put_prepared(blk.digest, blk.payload, blk.compressed)
+        entry["blocks"].append(blk.digest)
+        entry["block_lens"].append(blk.raw_len)
+
+    tensors: dict[str, dict] = {}
+    raw: dict[str, dict] = {}
+    on_device: list[tuple[dict, int, int, Any]] = []  # (entry, ptr, nbytes, keepalive)
+    if _registered_tensors:
+        import torch
+
+        for key, t in _registered_tensors.items():
+            nbytes = t.numel() * t.element_size()
+            entry = tensors[key] = entry_for(
+                nbytes,
+                dtype=str(t.dtype).removeprefix("torch."),
+                shape=tuple(t.shape),
+                was_cuda=t.is_cuda,
+            )
+            if nbytes == 0:
+                continue
+            src = t.detach().contiguous()
+            if src.is_cuda:
+                on_device.append((entry, src.data_ptr(), nbytes, src))
+            else:
+                # byte-level view: numpy() would reject bf16/fp8 dtypes
+                for blk in devcodec.encode_host(src.reshape(-1).view(torch.uint8).numpy()):
+                    add(entry, blk)
+    lib = rawmem.load_lib()
+    if lib is not None:
+        for key in rawmem._iter_keys(lib):
+            found = rawmem.lookup(key)
+            if found is None or (found[1] and not found[0]):
+                continue  # released (paged out) rows have no device memory
+            entry = raw[key] = entry_for(found[1])
+            if found[1]:
+                on_device.append((entry, found[0], found[1], None))
+    if on_device:
+        objects = [(ptr, nbytes) for _e, ptr, nbytes, _k in on_device]
+        for oi, blk in devcodec.iter_encode_device(objects, known=store.has):
+            add(on_device[oi][0], blk)
+    payload = {
+        "version": 2,
+        "tensors": tensors,
+        "raw": raw,
+        "rng": _rng_capture(),
+        "fidelity": rawmem.fidelity_report(),
+    }
+    return pickle.dumps(payload, 4)
+
+
+def _stored_chunks(entry: dict, store: Any):
+    """(byte offset, [(digest, raw_len, payload, compressed)]) a few blocks
+    at a time, in order."""
+    off = 0
+    digests, lens = entry["blocks"], entry["block_lens"]
+    for i in range(0, len(digests), _RESTORE_CHUNK_BLOCKS):
+        chunk = []
+        for digest, raw_len in zip(
+            digests[i : i + _RESTORE_CHUNK_BLOCKS], lens[i : i + _RESTORE_CHUNK_BLOCKS]
+        ):
+            stored, compressed = store.get_stored(digest)
+            chunk.append((digest, raw_len, stored, compressed))
+        yield off, chunk
+        off += sum(b[1] for b in chunk)
+
+
+def _decode_into(entry: dict, store: Any, ptr: int, decoded: list) -> None:
+    """Decode an object's blocks into device memory at ptr, unverified;
+    ``decoded`` collects what _restore_manifest verifies in one pass."""
+    from ..ops import devcodec
+
+    if sum(entry["block_lens"]) != entry["nbytes"]:
+        raise ValueError("snapshot manifest block lengths do not add up")
+    for off, chunk in _stored_chunks(entry, store):
+        devcodec.decode_to_device(chunk, ptr + off, sum(b[1] for b in chunk), verify=False)
+    decoded.append((ptr, list(zip(entry["blocks"], entry["block_lens"]))))
+
+
+def _restore_manifest(payload: dict, store: Any) -> None:
+    from ..ops import devcodec, rawmem
+
+    decoded: list = []  # device objects: (ptr, [(digest, raw_len)])
+    restored: dict[str, Any] = {}
+    for key, entry in payload.get("raw", {}).items():
+        ptr = rawmem.acquire(key, entry["nbytes"])
+        _decode_into(entry, store, ptr, decoded)
+    if payload.get("tensors"):
+        import torch
+
+        for key, entry in payload["tensors"].items():
+            dtype = getattr(torch, entry["dtype"])
+            nbytes = entry["nbytes"]
+            if entry["was_cuda"] and torch.cuda.is_available():
+                flat = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+                _decode_into(entry, store, flat.data_ptr(), decoded)
+            else:
+                data = bytearray()
+                for _off, chunk in _stored_chunks(entry, store):
+                    data += devcodec.decode_host(chunk)
+                if len(data) != nbytes:
+                    raise ValueError(f"snapshot tensor {key!r}: {len(data)} bytes, manifest {nbytes}")
+                flat = (
+                    torch.frombuffer(data, dtype=torch.uint8)
+                    if nbytes
+                    else torch.empty(0, dtype=torch.uint8)
+                )
+            restored[key] = flat.view(dtype).reshape(entry["shape"])
+    if decoded:
+        # every device object re-hashed against the manifest, the short
+        # blocks of all of them in one dispatch
+        devcodec.verify_device(decoded)
+    _restored_tensors.update(restored)
+    _registered_tensors.update(restored)
 
 
 def wait_and_restore_from_state_file(path: Optional[str] = None, timeout: float = 60.0) -> Optional[dict]:
@@ -312,8 +463,13 @@ def wait_and_restore_from_state_file(path: Optional[str] = None, timeout: float 
             os.environ[key] = str(value)
         blob_path = state.get("snapshot_path")
         if blob_path:
+            store = None
+            if state.get("blob_root"):
+                from ..scheduler.blobs import BlobStore
+
+                store = BlobStore(state["blob_root"])
             with open(blob_path, "rb") as f:
-                restore_payload(f.read())
+                restore_payload(f.read(), store)
         return state
     except BaseException:
         sys.exit(CUDA_CHECKPOINT_SENTINEL_EXIT)

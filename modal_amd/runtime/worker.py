@@ -195,6 +195,16 @@ class WorkerRPCTarget:
 
         return await asyncio.get_running_loop().run_in_executor(None, capture_payload)
 
+    async def snapshot_manifest(self) -> bytes:
+        """Block-addressed snapshot (gpu_snapshot.capture_manifest): the
+        state's blocks go straight into the shared CAS, encoded on the GPU
+        where they live; only the small manifest crosses the socket."""
+        from .gpu_snapshot import capture_manifest
+
+        return await asyncio.get_running_loop().run_in_executor(
+            None, capture_manifest, self._runtime.blob_store
+        )
+
 
 class FunctionRuntime:
     """Worker-side state for one registered function."""

@@ -166,6 +166,24 @@ class BlobStore:
                 pass
             raise
 
+    def put_prepared(self, digest: str, payload: bytes, compressed: bool) -> bool:
+        """Store a block its producer already hashed and encoded (the device
+        codec, ops/devcodec.py). False, and nothing written, when the CAS
+        already has the digest in either form."""
+        if self.has(digest):
+            return False
+        self._store_prepared(digest, payload, compressed)
+        return True
+
+    def get_stored(self, digest: str) -> tuple[bytes, bool]:
+        """The stored form, NOT decompressed: (payload, compressed)."""
+        path = self._path(digest)
+        if os.path.exists(path):
+            with open(path, "rb") as f:
+                return f.read(), False
+        with open(self._zpath(digest), "rb") as f:
+            return f.read(), True
+
     def put_file(self, src_path: str) -> str:
         # Same CAS key as put(): plain SHA-256 below the GPU threshold, the
         # domain-separated tree digest above (advisor finding: the two paths

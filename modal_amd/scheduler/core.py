@@ -1387,15 +1387,20 @@ class Scheduler:
         }
 
     # -- worker GPU snapshots ---------------------------------------------
-    async def worker_snapshot(self, worker_id: int) -> dict:
+    async def worker_snapshot(self, worker_id: int, block_addressed: bool = False) -> dict:
         """Capture a worker's snapshot-visible GPU state (registered
         tensors + tracked raw hipMalloc allocations + RNG) into the CAS.
         Parity: the snapshot half of ContainerCheckpoint
-        (reference task_lifecycle_manager.py:195)."""
+        (reference task_lifecycle_manager.py:195).
+
+        block_addressed=True: the worker encodes its state into CAS blocks
+        itself (on the GPU for device memory) and returns only a manifest
+        of digests; unchanged blocks of a later snapshot are stored once."""
         w = self.pool.workers.get(int(worker_id))
         if w is None:
             raise NotFoundError(f"worker {worker_id} not connected")
-        data = await w.conn.call("snapshot_state", timeout=300)
+        rpc = "snapshot_manifest" if block_addressed else "snapshot_state"
+        data = await w.conn.call(rpc, timeout=300)
         blob_id = self.blob_store.put(data)
         return {"snapshot_id": blob_id}
 
@@ -1413,6 +1418,7 @@ class Scheduler:
             "task_id": new_id("task"),
             "snapshot_id": snapshot_id,
             "snapshot_path": self.blob_store.open_path(snapshot_id),
+            "blob_root": self.blob_store.root,
             "env": {},
             "snapshot_debug": False,
         }
