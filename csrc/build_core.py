@@ -12,9 +12,21 @@ _REPO = os.path.dirname(_THIS)
 _OUT = os.path.join(_REPO, "modal_amd", f"_core{sysconfig.get_config_var('EXT_SUFFIX')}")
 
 
+def _sources() -> list[str]:
+    """core.cpp and every header under csrc/ (it includes them): a change
+    to any of these makes the module stale."""
+    return [os.path.join(_THIS, "core.cpp")] + sorted(
+        os.path.join(_THIS, name)
+        for name in os.listdir(_THIS)
+        if name.endswith((".h", ".hpp"))
+    )
+
+
 def needs_build() -> bool:
-    src = os.path.join(_THIS, "core.cpp")
-    return not os.path.exists(_OUT) or os.path.getmtime(src) > os.path.getmtime(_OUT)
+    if not os.path.exists(_OUT):
+        return True
+    built = os.path.getmtime(_OUT)
+    return any(os.path.getmtime(src) > built for src in _sources())
 
 
 def build(verbose: bool = True, force: bool = False) -> str:
@@ -28,6 +40,7 @@ def build(verbose: bool = True, force: bool = False) -> str:
         "-std=c++20",
         "-shared",
         "-fPIC",
+        "-pthread",
         f"-I{pybind11.get_include()}",
         f"-I{sysconfig.get_paths()['include']}",
         os.path.join(_THIS, "core.cpp"),

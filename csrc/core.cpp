@@ -9,7 +9,13 @@
 //    buffers in pinned host memory"). Large input/output frames ride the
 //    ring; the Unix socket stays the control/doorbell path. Lock-free
 //    (acquire/release atomics), frames length-prefixed, wrap-around via a
-//    skip sentinel. memcpy runs with the GIL released.
+//    skip sentinel. memcpy of large frames runs with the GIL released.
+//
+//  * RingHub / ChunkLane — the native chunk lane (ring.h, lane.h, both free
+//    of Python types): futex doorbells on the rings, one waiter thread per
+//    process that signals the event loop through an eventfd, and a
+//    dispatcher that places map chunks on workers, returns credit on
+//    chunk_done and refills, all inside one drain() call.
 //
 //  * pack_payloads / unpack_payloads — batch pickle-payload framing used by
 //    the map fan-out: N buffers <-> one contiguous [u32 len]* blob without
@@ -17,6 +23,9 @@
 
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
+
+#include "lane.h"
+#include "ring.h"
 
 #include <algorithm>
 #include <atomic>
@@ -37,144 +46,109 @@ namespace py = pybind11;
 
 namespace {
 
-struct RingHeader {
-  alignas(64) std::atomic<uint64_t> head;  // bytes produced
-  alignas(64) std::atomic<uint64_t> tail;  // bytes consumed
-  alignas(64) uint64_t capacity;
-  uint64_t magic;
-};
+using modal_amd::BellFile;
+using modal_amd::Ring;
+using modal_amd::RingHub;
 
-constexpr uint64_t kMagic = 0x6d6f64616c616d64ULL;  // "modalamd"
-constexpr uint32_t kSkip = 0xFFFFFFFFu;
+// frames this large are copied with the GIL released
+constexpr uint64_t kGilReleaseBytes = 64 * 1024;
 
-class ShmRing {
- public:
-  ShmRing(const std::string& path, uint64_t capacity, bool create) {
-    int flags = create ? (O_RDWR | O_CREAT) : O_RDWR;
-    fd_ = ::open(path.c_str(), flags, 0600);
-    if (fd_ < 0) throw std::runtime_error("ShmRing: open failed: " + path);
-    uint64_t total = sizeof(RingHeader) + capacity;
-    if (create) {
-      if (::ftruncate(fd_, (off_t)total) != 0) {
-        ::close(fd_);
-        throw std::runtime_error("ShmRing: ftruncate failed");
-      }
-    } else {
-      struct stat st;
-      if (::fstat(fd_, &st) != 0 || (uint64_t)st.st_size < sizeof(RingHeader)) {
-        ::close(fd_);
-        throw std::runtime_error("ShmRing: bad ring file");
-      }
-      total = (uint64_t)st.st_size;
-      capacity = total - sizeof(RingHeader);
-    }
-    void* mem = ::mmap(nullptr, total, PROT_READ | PROT_WRITE, MAP_SHARED, fd_, 0);
-    if (mem == MAP_FAILED) {
-      ::close(fd_);
-      throw std::runtime_error("ShmRing: mmap failed");
-    }
-    base_ = static_cast<uint8_t*>(mem);
-    header_ = reinterpret_cast<RingHeader*>(base_);
-    data_ = base_ + sizeof(RingHeader);
-    total_ = total;
-    if (create) {
-      header_->head.store(0, std::memory_order_relaxed);
-      header_->tail.store(0, std::memory_order_relaxed);
-      header_->capacity = capacity;
-      header_->magic = kMagic;
-    } else if (header_->magic != kMagic) {
-      throw std::runtime_error("ShmRing: magic mismatch");
-    }
-    capacity_ = header_->capacity;
+// producer: returns false when the frame does not fit right now
+bool ring_push(Ring& ring, py::buffer buf) {
+  py::buffer_info info = buf.request();
+  const uint8_t* src = static_cast<const uint8_t*>(info.ptr);
+  const uint64_t n = (uint64_t)info.size * (uint64_t)info.itemsize;
+  uint8_t* dst = ring.reserve(n);
+  if (!dst) return false;
+  if (n >= kGilReleaseBytes) {
+    py::gil_scoped_release release;
+    std::memcpy(dst, src, n);
+  } else {
+    std::memcpy(dst, src, n);
   }
+  ring.commit();
+  return true;
+}
 
-  ~ShmRing() {
-    if (base_) ::munmap(base_, total_);
-    if (fd_ >= 0) ::close(fd_);
+// consumer: drain up to max_frames frames (0 = all available)
+py::list ring_pop_all(Ring& ring, size_t max_frames) {
+  py::list out;
+  ring.pop(
+      [&](const uint8_t* ptr, size_t len) {
+        out.append(py::bytes(reinterpret_cast<const char*>(ptr), len));
+      },
+      max_frames);
+  return out;
+}
+
+// every frame of every ring of the hub, in ring order: [(slot, bytes)]
+py::list hub_drain(RingHub& hub) {
+  py::list out;
+  hub.drain([&](int slot, const uint8_t* ptr, size_t len) {
+    out.append(py::make_tuple(slot, py::bytes(reinterpret_cast<const char*>(ptr), len)));
+  });
+  return out;
+}
+
+using modal_amd::Assignment;
+using modal_amd::ChunkDone;
+using modal_amd::ChunkLane;
+using modal_amd::FrameKind;
+
+py::str sv_str(std::string_view s) { return py::str(s.data(), s.size()); }
+
+// (token, call_id, chunk_id, function_id, count, data, cis)
+py::tuple done_tuple(const ChunkDone& d) {
+  py::object cis = py::none();
+  if (!d.cis_nil) {
+    py::list items;
+    for (int64_t v : d.cis) items.append(py::int_(v));
+    cis = std::move(items);
   }
+  return py::make_tuple(sv_str(d.token), sv_str(d.call_id), sv_str(d.chunk_id),
+                        sv_str(d.function_id), py::int_(d.count),
+                        py::bytes(d.data.data(), d.data.size()), cis);
+}
 
-  ShmRing(const ShmRing&) = delete;
-  ShmRing& operator=(const ShmRing&) = delete;
+py::list assignment_list(const std::vector<Assignment>& assignments) {
+  py::list out;
+  for (const auto& a : assignments) out.append(py::make_tuple(a.token, a.worker_slot));
+  return out;
+}
 
-  // producer: returns false when the frame does not fit right now
-  bool push(py::buffer buf) {
-    py::buffer_info info = buf.request();
-    const uint8_t* src = static_cast<const uint8_t*>(info.ptr);
-    const uint64_t n = (uint64_t)info.size * (uint64_t)info.itemsize;
-    if (n + 8 > capacity_) throw std::runtime_error("frame larger than ring");
-    uint64_t head = header_->head.load(std::memory_order_relaxed);
-    uint64_t tail = header_->tail.load(std::memory_order_acquire);
-    uint64_t pos = head % capacity_;
-    uint64_t to_end = capacity_ - pos;
-    uint64_t need = 4 + n;
-    uint64_t skip = 0;
-    if (to_end < 4) {
-      skip = to_end;  // too small even for a length: pad to start
-    } else if (to_end < need) {
-      // write a skip sentinel and start the frame at offset 0
-      skip = to_end;
-    }
-    if (head + skip + need - tail > capacity_) return false;  // full
-    {
-      py::gil_scoped_release release;
-      if (skip) {
-        if (to_end >= 4) {
-          uint32_t sentinel = kSkip;
-          std::memcpy(data_ + pos, &sentinel, 4);
-        }
-        pos = 0;
-      }
-      uint32_t len32 = (uint32_t)n;
-      std::memcpy(data_ + pos, &len32, 4);
-      std::memcpy(data_ + pos + 4, src, n);
-    }
-    header_->head.store(head + skip + need, std::memory_order_release);
-    return true;
-  }
+// the clean tuple, or None for a frame Python has to read itself
+py::object parse_chunk_done_py(py::buffer buf) {
+  py::buffer_info info = buf.request();
+  ChunkDone done;
+  FrameKind kind = modal_amd::parse_chunk_done(
+      static_cast<const uint8_t*>(info.ptr), (size_t)info.size * (size_t)info.itemsize, &done);
+  if (kind != FrameKind::kDoneClean) return py::none();
+  return done_tuple(done);
+}
 
-  // consumer: drain up to max_frames frames (0 = all available)
-  py::list pop_all(size_t max_frames = 0) {
-    py::list out;
-    uint64_t tail = header_->tail.load(std::memory_order_relaxed);
-    uint64_t head = header_->head.load(std::memory_order_acquire);
-    size_t count = 0;
-    while (tail < head) {
-      uint64_t pos = tail % capacity_;
-      uint64_t to_end = capacity_ - pos;
-      if (to_end < 4) {
-        tail += to_end;  // padding at end (no room for a length)
-        continue;
-      }
-      uint32_t len32;
-      std::memcpy(&len32, data_ + pos, 4);
-      if (len32 == kSkip) {
-        tail += to_end;
-        continue;
-      }
-      py::bytes frame(reinterpret_cast<const char*>(data_ + pos + 4), len32);
-      out.append(std::move(frame));
-      tail += 4 + len32;
-      if (max_frames && ++count >= max_frames) break;
-    }
-    header_->tail.store(tail, std::memory_order_release);
-    return out;
-  }
+int lane_submit(ChunkLane& lane, int fn_slot, const std::string& token, uint64_t count,
+                py::buffer frame, bool front) {
+  py::buffer_info info = frame.request();
+  return lane.submit(fn_slot, token, count, static_cast<const uint8_t*>(info.ptr),
+                     (size_t)info.size * (size_t)info.itemsize, front);
+}
 
-  uint64_t pending_bytes() const {
-    return header_->head.load(std::memory_order_acquire) -
-           header_->tail.load(std::memory_order_acquire);
-  }
-
-  uint64_t capacity() const { return capacity_; }
-
- private:
-  int fd_ = -1;
-  uint8_t* base_ = nullptr;
-  uint8_t* data_ = nullptr;
-  RingHeader* header_ = nullptr;
-  uint64_t capacity_ = 0;
-  uint64_t total_ = 0;
-};
+// (completions[(worker_slot, clean tuple)], raw_frames[(worker_slot, bytes)],
+//  assignments[(token, worker_slot)])
+py::tuple lane_drain(ChunkLane& lane, RingHub& hub) {
+  py::list completions, raw;
+  std::vector<Assignment> assignments;
+  lane.drain(
+      hub,
+      [&](int slot, const ChunkDone& done) {
+        completions.append(py::make_tuple(slot, done_tuple(done)));
+      },
+      [&](int slot, const uint8_t* ptr, size_t len) {
+        raw.append(py::make_tuple(slot, py::bytes(reinterpret_cast<const char*>(ptr), len)));
+      },
+      &assignments);
+  return py::make_tuple(completions, raw, assignment_list(assignments));
+}
 
 py::bytes pack_payloads(const std::vector<py::bytes>& items) {
   uint64_t total = 0;
@@ -561,13 +535,65 @@ static int64_t spawn_supervised(const std::vector<std::string>& argv,
 
 PYBIND11_MODULE(_core, m) {
   m.doc() = "modal_amd native core: shm ring transport + batch framing";
-  py::class_<ShmRing>(m, "ShmRing")
+  py::class_<BellFile, std::shared_ptr<BellFile>>(m, "BellFile")
+      .def(py::init<const std::string&, bool>(), py::arg("path"), py::arg("create") = false);
+  py::class_<Ring, std::shared_ptr<Ring>>(m, "ShmRing")
       .def(py::init<const std::string&, uint64_t, bool>(), py::arg("path"),
            py::arg("capacity") = (uint64_t)64 << 20, py::arg("create") = false)
-      .def("push", &ShmRing::push)
-      .def("pop_all", &ShmRing::pop_all, py::arg("max_frames") = 0)
-      .def("pending_bytes", &ShmRing::pending_bytes)
-      .def("capacity", &ShmRing::capacity);
+      .def("push", &ring_push)
+      .def("pop_all", &ring_pop_all, py::arg("max_frames") = 0)
+      .def("pending_bytes", &Ring::pending_bytes)
+      .def("capacity", &Ring::capacity)
+      .def("too_large", &Ring::too_large)
+      .def("bell_wakes", &Ring::bell_wakes)
+      .def("set_shared_bell", &Ring::set_shared_bell);
+  py::class_<RingHub>(m, "RingHub")
+      .def(py::init<const std::string&, int>(), py::arg("bell_path") = "",
+           py::arg("timeout_ms") = 20)
+      .def("add_ring", &RingHub::add_ring)
+      .def("remove_ring", &RingHub::remove_ring)
+      .def("fd", &RingHub::fd)
+      .def("drain", &hub_drain)
+      // joins the waiter with the GIL held: the waiter never takes it, and a
+      // daemon thread that gave it up here could be ended inside this frame
+      // by interpreter shutdown
+      .def("close", &RingHub::close)
+      .def("stats", [](RingHub& hub) {
+        py::dict d;
+        d["notifies"] = hub.notifies();
+        d["waits"] = hub.waits();
+        d["drains"] = hub.drains();
+        d["producer_wakes"] = hub.producer_wakes();
+        d["rings"] = hub.ring_count();
+        return d;
+      });
+  py::class_<ChunkLane>(m, "ChunkLane")
+      .def(py::init<>())
+      .def("add_worker", &ChunkLane::add_worker)
+      .def("remove_worker", &ChunkLane::remove_worker)
+      .def("set_eligible", &ChunkLane::set_eligible)
+      .def("set_cap", &ChunkLane::set_cap, py::arg("fn_slot"), py::arg("items"),
+           py::arg("min_chunks") = 1)
+      .def("submit", &lane_submit, py::arg("fn_slot"), py::arg("token"), py::arg("count"),
+           py::arg("frame"), py::arg("front") = false)
+      .def("kick", [](ChunkLane& lane, int fn_slot) {
+        std::vector<Assignment> out;
+        lane.kick(fn_slot, &out);
+        return assignment_list(out);
+      })
+      .def("complete", [](ChunkLane& lane, int worker_slot, const std::string& token) {
+        std::vector<Assignment> out;
+        lane.complete(worker_slot, token, &out);
+        return assignment_list(out);
+      })
+      .def("cancel", &ChunkLane::cancel)
+      .def("drop_queue", &ChunkLane::drop_queue)
+      .def("drain", &lane_drain)
+      .def("queued", &ChunkLane::queued)
+      .def("inflight", &ChunkLane::inflight)
+      .def("outstanding_items", &ChunkLane::outstanding_items)
+      .def("pushed", &ChunkLane::pushed);
+  m.def("parse_chunk_done", &parse_chunk_done_py);
   m.def("pack_payloads", &pack_payloads);
   m.def("malz_compress", &malz_compress, py::arg("data"), py::arg("min_gain") = 0.95);
   m.def("malz_decompress", &malz_decompress);

@@ -502,6 +502,22 @@ class WorkerRuntime:
             except Exception:
                 return
 
+    def _handle_sync(self, msg: dict) -> bool:
+        """Lane fast path: start a chunk straight from the hub drain. Every
+        other kind (and a chunk for an unknown function) goes to _handle."""
+        if msg.get("t") != "inputs_chunk":
+            return False
+        frt = self.functions.get(msg["function_id"])
+        if frt is None:
+            return False
+        self._start_chunk(frt, msg)
+        return True
+
+    def _start_chunk(self, frt: "FunctionRuntime", msg: dict) -> None:
+        task = asyncio.get_running_loop().create_task(self._run_chunk(frt, msg))
+        self._running[msg["token"]] = task
+        task.add_done_callback(lambda _t, tok=msg["token"]: self._running.pop(tok, None))
+
     async def _handle(self, msg: dict) -> None:
         kind = msg.get("t")
         if kind == "hello_ack":
@@ -509,7 +525,21 @@ class WorkerRuntime:
             os.environ["MODAL_AMD_TASK_ID"] = self.task_id
             if msg.get("ring_in"):
                 # worker's out-ring is the scheduler's in-ring and vice versa
-                self.conn.attach_rings(msg.get("ring_out"), msg.get("ring_in"), create=False)
+                attached = self.conn.attach_rings(
+                    msg.get("ring_out"), msg.get("ring_in"), create=False
+                )
+                if attached and msg.get("lane_bell"):
+                    # native lane: from here on both directions ride the rings
+                    self.conn.sync_handler = self._handle_sync
+                    attached = self.conn.enable_lane(shared_bell=msg["lane_bell"], own_hub=True)
+                if msg.get("lane_bell") and not attached:
+                    # the scheduler already puts every frame for us on the
+                    # ring: a worker that cannot read it must not linger
+                    sys.__stderr__.write(
+                        f"worker {self.worker_id}: cannot attach the native lane, closing\n"
+                    )
+                    self._shutdown.set()  # run() closes the connection
+                    return
             self._hello_ack.set()
         elif kind == "def":
             frt = FunctionRuntime(self, msg)
@@ -574,11 +604,7 @@ class WorkerRuntime:
                     }
                 )
                 return
-            task = asyncio.get_running_loop().create_task(self._run_chunk(frt, msg))
-            self._running[msg["token"]] = task
-            task.add_done_callback(
-                lambda _t, tok=msg["token"]: self._running.pop(tok, None)
-            )
+            self._start_chunk(frt, msg)
         elif kind == "cancel":
             for token in msg.get("tokens", []):
                 task = self._running.get(token)
@@ -962,39 +988,44 @@ class WorkerRuntime:
                         self.executor, self._chunk_pairs, msg["chunk_id"]
                     )
                     bsz = frt.batch_max_size
-                    for start in range(0, count, bsz):
-                        idxs = range(start, min(start + bsz, count))
-                        try:
-                            arglists, kwlists = _transpose(pairs, kw_common, idxs)
-                            if is_async:
-                                results = await self._execute(frt, fn0, arglists, kwlists)
-                            else:
+                    # like _run_batch, a chunk's batches hold frt.sem: with
+                    # two chunks in flight on this worker the user's batched
+                    # function still runs one call at a time (max_concurrent
+                    # of them under @concurrent), the next chunk queued behind
+                    async with frt.sem:
+                        for start in range(0, count, bsz):
+                            idxs = range(start, min(start + bsz, count))
+                            try:
+                                arglists, kwlists = _transpose(pairs, kw_common, idxs)
+                                if is_async:
+                                    results = await self._execute(frt, fn0, arglists, kwlists)
+                                else:
 
-                                def _call_batch(
-                                    arglists: tuple = arglists, kwlists: dict = kwlists
-                                ) -> Any:
-                                    # executor threads carry their own context
-                                    tok_c = _current_function_call_id.set(call_id)
-                                    tok_a2 = _app_id_var.set(frt.app_id)
-                                    try:
-                                        return fn0(*arglists, **kwlists)
-                                    finally:
-                                        _current_function_call_id.reset(tok_c)
-                                        _app_id_var.reset(tok_a2)
+                                    def _call_batch(
+                                        arglists: tuple = arglists, kwlists: dict = kwlists
+                                    ) -> Any:
+                                        # executor threads carry their own context
+                                        tok_c = _current_function_call_id.set(call_id)
+                                        tok_a2 = _app_id_var.set(frt.app_id)
+                                        try:
+                                            return fn0(*arglists, **kwlists)
+                                        finally:
+                                            _current_function_call_id.reset(tok_c)
+                                            _app_id_var.reset(tok_a2)
 
-                                results = await loop.run_in_executor(
-                                    self.executor, _call_batch
-                                )
-                            _store(idxs, results)
-                        except (asyncio.CancelledError, InputCancellation):
-                            raise  # cancel: abort the chunk, don't mark failed
-                        except BaseException as exc:
-                            data = self._serialize_exception(exc)
-                            err = "".join(
-                                traceback.format_exception_only(type(exc), exc)
-                            ).strip()
-                            for ci in idxs:
-                                errors[ci] = (data, err)
+                                    results = await loop.run_in_executor(
+                                        self.executor, _call_batch
+                                    )
+                                _store(idxs, results)
+                            except (asyncio.CancelledError, InputCancellation):
+                                raise  # cancel: abort the chunk, don't mark failed
+                            except BaseException as exc:
+                                data = self._serialize_exception(exc)
+                                err = "".join(
+                                    traceback.format_exception_only(type(exc), exc)
+                                ).strip()
+                                for ci in idxs:
+                                    errors[ci] = (data, err)
                 except (asyncio.CancelledError, InputCancellation):
                     raise
                 except BaseException as exc:

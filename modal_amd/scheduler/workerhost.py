@@ -18,7 +18,9 @@ import subprocess
 import sys
 import time
 from collections import deque
-from typing import TYPE_CHECKING, Optional
+from typing import TYPE_CHECKING, Any, Optional
+
+import msgpack
 
 from ..utils.ids import new_id
 from .calls import (
@@ -27,7 +29,7 @@ from .calls import (
     FunctionDef,
     InputRecord,
 )
-from .transport import Connection
+from .transport import Connection, _core, native_lane_enabled
 
 _CPU_COUNT = os.cpu_count()  # cached: _pool_limit runs per dispatch
 
@@ -38,6 +40,14 @@ if TYPE_CHECKING:
 # the analog of the reference's 49-inputs-per-PutInputs batching
 # (/root/reference/py/modal/parallel_map.py:82) tuned for a local socket.
 DEFAULT_PIPELINE_DEPTH = 256
+
+# native lane credit: a worker may hold max(credit_cap items, this many
+# chunks). 2 keeps a successor in flight behind a chunk as large as the cap;
+# measured on MI355X the refill inside the lane's drain is quick enough that
+# 1 wins (profiles/README.md, "Native chunk lane")
+LANE_MIN_CHUNKS = max(1, int(os.environ.get("MODAL_AMD_LANE_MIN_CHUNKS", "1")))
+# larger frames keep the Python dispatch road (and its error handling)
+LANE_MAX_FRAME = 8 << 20
 
 
 class WorkerHandle:
@@ -68,18 +78,25 @@ class WorkerHandle:
         self.defs_version: dict[str, int] = {}
         self.chunks_sent: set[str] = set()
         self.draining = False
+        self.hub_slot: Optional[int] = None  # this worker's ring in the pool's hub
+        self.lane_fns: set[str] = set()  # functions the lane may place here
 
     @property
     def has_gpu(self) -> bool:
         return self.gpu_index is not None
 
     def credit_for(self, fdef: FunctionDef) -> int:
-        # deep enough for >=3 chunk groups in flight so a worker never idles
-        # between group completions (map chunks are ~64 items each)
-        cap = max(fdef.max_concurrent_inputs * 2, DEFAULT_PIPELINE_DEPTH)
-        if fdef.batch_max_size:
-            cap = max(cap, fdef.batch_max_size * 2)
-        return cap - self.outstanding.get(fdef.function_id, 0)
+        return credit_cap(fdef) - self.outstanding.get(fdef.function_id, 0)
+
+
+def credit_cap(fdef: FunctionDef) -> int:
+    """Items a worker may hold of one function. Deep enough for >=3 chunk
+    groups of ~64 items in flight; for larger chunks the lane can keep
+    LANE_MIN_CHUNKS chunks in flight instead."""
+    cap = max(fdef.max_concurrent_inputs * 2, DEFAULT_PIPELINE_DEPTH)
+    if fdef.batch_max_size:
+        cap = max(cap, fdef.batch_max_size * 2)
+    return cap
 
 
 class WorkerPool:
@@ -103,10 +120,209 @@ class WorkerPool:
         self._pending_spawns = 0
         self._worker_ready = asyncio.Event()
         self._procs: list[subprocess.Popen] = []
+        # native lane: one hub waits on every worker's outbound ring
+        self._hub: Any = None
+        self._hub_bell = os.path.join(self.run_dir, "hub.bell")
+        self._hub_conns: dict[int, Connection] = {}
+        self._next_hub_slot = 0
+        # native chunk dispatcher (csrc/lane.h). Python keeps the records:
+        # token -> (record, group) for every chunk the lane holds, queued or
+        # in flight, and applies the assignments the lane reports.
+        self._lane: Any = None
+        self._lane_workers: dict[int, WorkerHandle] = {}
+        self._lane_fn_slots: dict[str, int] = {}
+        self._lane_fn_version: dict[str, Optional[int]] = {}
+        self._lane_groups: dict[str, tuple] = {}
+        self._lane_refresh_fns: set[str] = set()
 
     # -- lifecycle -------------------------------------------------------
+    def _start_hub(self) -> None:
+        if not native_lane_enabled():
+            return
+        try:
+            self._hub = _core.RingHub(self._hub_bell, 20)
+            self._lane = _core.ChunkLane()
+            asyncio.get_running_loop().add_reader(self._hub.fd(), self._on_hub_ready)
+        except Exception as exc:
+            self._hub = None
+            self._lane = None
+            self.scheduler.log(f"native lane unavailable: {exc!r}")
+
+    def _stop_hub(self) -> None:
+        hub, self._hub = self._hub, None
+        self._lane = None
+        if hub is not None:
+            try:
+                asyncio.get_running_loop().remove_reader(hub.fd())
+            except Exception:
+                pass
+            hub.close()
+        self._hub_conns.clear()
+        self._lane_workers.clear()
+
+    def _on_hub_ready(self) -> None:
+        """The hub's eventfd fired. One native call pops every frame of every
+        worker's ring, returns the credit of each chunk_done and pushes the
+        queued chunks that credit allows; what is left for Python is to
+        record the completions and the new assignments."""
+        hub, lane = self._hub, self._lane
+        if hub is None or lane is None:
+            return
+        completions, raw_frames, assignments = lane.drain(hub)
+        # Assignments first: a chunk's push always precedes its chunk_done,
+        # so a chunk pushed and completed within this one drain is recorded
+        # as assigned before its completion takes it out again.
+        for token, slot in assignments:
+            self._lane_assigned(token, slot)
+        workers = self._lane_workers
+        for slot, fields in completions:
+            w = workers.get(slot)
+            if w is not None:
+                w.conn.ring_frames_received += 1
+                try:
+                    self._chunk_done_fields(w, *fields)
+                except Exception as exc:  # pragma: no cover - defensive
+                    self.scheduler.log(f"lane completion error: {exc!r}")
+        conns = self._hub_conns
+        for slot, body in raw_frames:
+            conn = conns.get(slot)
+            if conn is not None:
+                try:
+                    conn.on_ring_frame(body)
+                except Exception as exc:  # pragma: no cover - defensive
+                    self.scheduler.log(f"lane frame error: {exc!r}")
+
+    # -- native lane -----------------------------------------------------
+    def _lane_fn_slot(self, fdef: FunctionDef) -> int:
+        fid = fdef.function_id
+        slot = self._lane_fn_slots.get(fid)
+        if slot is None:
+            slot = self._lane_fn_slots[fid] = len(self._lane_fn_slots)
+            self._lane_fn_version[fid] = None
+        if self._lane_fn_version[fid] != fdef.definition_version:
+            # (re)defined: no worker holds this version yet
+            for w in self._lane_workers.values():
+                if fid in w.lane_fns:
+                    w.lane_fns.discard(fid)
+                    self._lane.set_eligible(slot, w.hub_slot, False)
+            self._lane.set_cap(slot, credit_cap(fdef), LANE_MIN_CHUNKS)
+            self._lane_fn_version[fid] = fdef.definition_version
+        return slot
+
+    def _lane_submit(self, record: Any, group: Any, fdef: FunctionDef, front: bool) -> bool:
+        """Hand a chunk group to the lane. False: the lane cannot carry it and
+        the caller queues it for _dispatch_once."""
+        if self._lane is None or not self._lane_workers:
+            return False
+        chunk = record.chunks.get(group.chunk_id) or {}
+        frame = msgpack.packb(
+            {
+                "t": "inputs_chunk",
+                "function_id": fdef.function_id,
+                "call_id": record.call_id,
+                "chunk_id": group.chunk_id,
+                "token": group.token,
+                "count": group.count,
+                "payload": chunk.get("data"),
+                "method": group.method,
+                "max_concurrent": fdef.max_concurrent_inputs,
+            },
+            use_bin_type=True,
+        )
+        if len(frame) > LANE_MAX_FRAME:
+            return False
+        fn_slot = self._lane_fn_slot(fdef)
+        token = group.token
+        self._lane_groups[token] = (record, group)
+        slot = self._lane.submit(fn_slot, token, group.count, frame, front)
+        if slot >= 0:
+            self._lane_assigned(token, slot)
+        else:
+            # no eligible worker with credit: ensure_workers, def pushes and
+            # autoscale are _dispatch_once's business
+            self._lane_refresh_fns.add(fdef.function_id)
+            self._dispatch_wake.set()
+        return True
+
+    def _lane_assigned(self, token: str, slot: int) -> None:
+        """The lane pushed this chunk to that worker: what _send_group records."""
+        entry = self._lane_groups.get(token)
+        w = self._lane_workers.get(slot)
+        if entry is None or w is None:
+            return
+        record, group = entry
+        group.state = "inflight"
+        group.worker_id = w.worker_id
+        w.last_active = time.time()
+        w.inflight[token] = ("g", record, group)
+        w.conn.ring_frames_sent += 1
+        fid = record.function_id
+        w.outstanding[fid] = w.outstanding.get(fid, 0) + group.count
+
+    def _lane_revoke(self, w: WorkerHandle) -> None:
+        """Stop placing new chunks on this worker (draining, paged, dead)."""
+        if self._lane is not None and w.hub_slot is not None:
+            for fid in w.lane_fns:
+                self._lane.set_eligible(self._lane_fn_slots[fid], w.hub_slot, False)
+        w.lane_fns.clear()
+
+    async def _lane_dispatch(self) -> None:
+        """The exceptional half of lane dispatch: bring workers up, push
+        defs, restore paged workers, then let the lane place its queue."""
+        lane = self._lane
+        for fid in list(self._lane_refresh_fns):
+            self._lane_refresh_fns.discard(fid)
+            fn_slot = self._lane_fn_slots.get(fid)
+            if lane is None or fn_slot is None:
+                continue
+            fdef = self.scheduler.functions.get(fid)
+            if fdef is None:
+                for token in lane.drop_queue(fn_slot):
+                    self._lane_groups.pop(token, None)
+                continue
+            fn_slot = self._lane_fn_slot(fdef)
+            await self.ensure_workers(fdef.needs_gpu)
+            candidates = [
+                w
+                for w in self.workers.values()
+                if w.alive and not w.draining and (w.has_gpu or not fdef.needs_gpu)
+            ]
+            candidates = self._apply_placement(fdef, candidates)
+            chosen = {w.worker_id for w in candidates}
+            for w in list(self._lane_workers.values()):
+                if fid in w.lane_fns and w.worker_id not in chosen:
+                    w.lane_fns.discard(fid)
+                    lane.set_eligible(fn_slot, w.hub_slot, False)
+            for w in candidates:
+                if w.hub_slot is None or (fid in w.lane_fns and not w.paged):
+                    continue
+                try:
+                    await self._ensure_unpaged(w)
+                    if w.defs_version.get(fid, 0) != fdef.definition_version or (
+                        fid not in w.functions_loaded
+                    ):
+                        await self._send_def(w, fdef)
+                except Exception:
+                    continue
+                if (
+                    w.alive
+                    and not w.draining
+                    and not w.paged
+                    and w.hub_slot in self._lane_workers
+                    and self._lane_fn_version.get(fid) == fdef.definition_version
+                ):
+                    # the def is on the ring ahead of any chunk pushed from here on
+                    w.lane_fns.add(fid)
+                    lane.set_eligible(fn_slot, w.hub_slot, True)
+            for token, slot in lane.kick(fn_slot):
+                self._lane_assigned(token, slot)
+            backlog = lane.queued(fn_slot)
+            if backlog:
+                await self._maybe_scale_up(fdef, backlog=backlog, active=len(candidates))
+
     async def start(self) -> None:
         os.makedirs(self.run_dir, exist_ok=True)
+        self._start_hub()
         self._server = await asyncio.start_unix_server(self._on_connect, path=self.socket_path)
         try:
             os.chmod(self.socket_path, 0o600)
@@ -145,6 +361,7 @@ class WorkerPool:
                 # (parity: the reference's memory-snapshot cold-start
                 # elimination, gpu_memory_snapshot.py:230-300). Reversible,
                 # so not subject to the warm floor.
+                self._lane_revoke(w)
                 w.paged = True  # BEFORE the await: a concurrent dispatch
                 # must see it and queue a gpu_restore, which the worker's
                 # snapshot lock orders strictly after this page-out
@@ -160,6 +377,7 @@ class WorkerPool:
         excess = alive - max(floor, 1)
         for w in reapable[: max(excess, 0)]:
             w.draining = True
+            self._lane_revoke(w)
             try:
                 await w.conn.send({"t": "shutdown"})
             except Exception:
@@ -228,6 +446,7 @@ class WorkerPool:
                     w.proc.kill()
         for w in list(self.workers.values()):
             await w.conn.close()
+        self._stop_hub()
         # reap any process that never connected (or is still exiting)
         for proc in self._procs:
             if proc.poll() is None:
@@ -360,14 +579,35 @@ class WorkerPool:
                         external=bool(msg.get("external")),
                     )
                     handle_holder["h"] = handle
-                    self.workers[worker_id] = handle
-                    self._pending_spawns = max(0, self._pending_spawns - 1)
-                    self._worker_ready.set()
-                    self._dispatch_wake.set()
                     # shm ring pair: bulk frames bypass the socket
                     to_worker = os.path.join(self.run_dir, f"ring.{handle.task_id}.in")
                     from_worker = os.path.join(self.run_dir, f"ring.{handle.task_id}.out")
                     rings_ok = conn.attach_rings(to_worker, from_worker, create=True)
+                    # The lane is switched on before the handle can be seen by
+                    # dispatch, so a def and the chunks after it take the same
+                    # road (the ring) in order; only the ack below is forced
+                    # onto the socket.
+                    lane = rings_ok and self._hub is not None and conn.enable_lane()
+                    if lane:
+                        # registered before the ack: the worker may push the
+                        # moment it has attached
+                        handle.hub_slot = self._next_hub_slot
+                        self._next_hub_slot += 1
+                        self._hub_conns[handle.hub_slot] = conn
+                        self._hub.add_ring(handle.hub_slot, conn.ring_in)
+                        self._lane.add_worker(handle.hub_slot, conn.ring_out)
+                        self._lane_workers[handle.hub_slot] = handle
+                        conn.sync_handler = lambda m, h=handle: self._on_lane_frame(h, m)
+                        # functions with chunks in the lane get their def
+                        # pushed here on the next dispatch
+                        self._lane_refresh_fns.update(
+                            rec.function_id for rec, _g in self._lane_groups.values()
+                        )
+                    self.workers[worker_id] = handle
+                    self._pending_spawns = max(0, self._pending_spawns - 1)
+                    self._worker_ready.set()
+                    self._dispatch_wake.set()
+                    # the worker attaches its rings only on reading the ack
                     await conn.send(
                         {
                             "t": "hello_ack",
@@ -375,7 +615,9 @@ class WorkerPool:
                             "worker_id": worker_id,
                             "ring_in": to_worker if rings_ok else None,
                             "ring_out": from_worker if rings_ok else None,
-                        }
+                            "lane_bell": self._hub_bell if lane else None,
+                        },
+                        via_socket=True,
                     )
                     asyncio.get_running_loop().create_task(self._watch_worker(handle))
                 else:
@@ -411,20 +653,55 @@ class WorkerPool:
         conn = Connection(reader, writer, handler, rpc_target=None)  # set after auth
         conn.start()
 
+    def _on_lane_frame(self, handle: WorkerHandle, msg: dict) -> bool:
+        """The completion kinds whose handlers never suspend, served straight
+        from the hub drain; anything else takes the connection's inbox."""
+        kind = msg.get("t")
+        if kind == "chunk_done":
+            self._on_chunk_done(handle, msg)
+        elif kind == "outputs":
+            self._on_outputs(handle, msg)
+        elif kind == "outputs_chunk":
+            self._on_outputs_chunk(handle, msg)
+        elif kind == "hb":
+            handle.last_heartbeat = time.time()
+            if msg.get("gpu"):
+                handle.gpu_stats = msg["gpu"]
+        else:
+            return False
+        return True
+
     async def _watch_worker(self, handle: WorkerHandle) -> None:
         await handle.conn.wait_closed()
         handle.alive = False
         self.workers.pop(handle.worker_id, None)
+        lost: list[str] = []
+        if handle.hub_slot is not None:
+            self._hub_conns.pop(handle.hub_slot, None)
+            self._lane_workers.pop(handle.hub_slot, None)
+            handle.lane_fns.clear()
+            if self._hub is not None:
+                self._hub.remove_ring(handle.hub_slot)
+            if self._lane is not None:
+                lost = self._lane.remove_worker(handle.hub_slot)
         if self._stopping:
             return
+        for token in lost:
+            # the lane's view of what was in flight there; every assignment
+            # has been applied, so these are already in handle.inflight
+            entry = self._lane_groups.get(token)
+            if entry is not None and token not in handle.inflight:
+                handle.inflight[token] = ("g", entry[0], entry[1])
         # requeue in-flight inputs: the INTERNAL_FAILURE path
         for token, entry in list(handle.inflight.items()):
             if type(entry) is tuple:  # chunk group
                 _tag, record, group = entry
                 if group.state == "done" or record.cancelled:
+                    self._lane_groups.pop(token, None)
                     continue
                 group.internal_failures += 1
                 if group.internal_failures > MAX_INTERNAL_FAILURE_COUNT:
+                    self._lane_groups.pop(token, None)
                     for ci in range(group.count):
                         rec = record.materialize_chunk_item(group, ci)
                         self.scheduler.finalize_input(
@@ -542,7 +819,12 @@ class WorkerPool:
         self._dispatch_wake.set()
 
     def enqueue_chunk(self, record: Any, group: Any, function_id: str, front: bool = False) -> None:
-        """Queue a whole chunk group as one pending descriptor."""
+        """Queue a whole chunk group: on the native lane when it can carry
+        it, else as one pending descriptor for _dispatch_once."""
+        if self._lane is not None:
+            fdef = self.scheduler.functions.get(function_id)
+            if fdef is not None and self._lane_submit(record, group, fdef, front):
+                return
         q = self.pending.setdefault(function_id, deque())
         entry = ("g", record, group)
         if front:
@@ -587,6 +869,9 @@ class WorkerPool:
                 self.scheduler.log(f"dispatch error: {exc!r}")
 
     async def _dispatch_once(self) -> None:
+        if self._lane_refresh_fns:
+            await self._lane_dispatch()
+        # lane-owned groups never enter self.pending
         for fid, q in list(self.pending.items()):
             if not q:
                 continue
@@ -810,21 +1095,59 @@ class WorkerPool:
                 self.enqueue_chunk(record, group, fdef.function_id, front=True)
 
     def _on_chunk_done(self, handle: WorkerHandle, msg: dict) -> None:
-        """Completion of a range-protocol chunk."""
+        """Completion of a range-protocol chunk, as a decoded frame."""
+        if self._lane is not None and handle.hub_slot is not None:
+            # arrived by socket (a frame sent before the lane was up):
+            # the lane still has to return the credit
+            for token, slot in self._lane.complete(handle.hub_slot, msg["token"]):
+                self._lane_assigned(token, slot)
+        self._chunk_done_fields(
+            handle,
+            msg["token"],
+            msg["call_id"],
+            msg["chunk_id"],
+            msg.get("function_id"),
+            msg.get("count", 0),
+            msg.get("data"),
+            msg.get("cis"),
+            msg.get("failed"),
+            msg.get("exceptions"),
+            msg.get("items"),
+        )
+
+    def _chunk_done_fields(
+        self,
+        handle: WorkerHandle,
+        token: str,
+        call_id: str,
+        chunk_id: str,
+        fid: Optional[str],
+        count: int,
+        data: Optional[bytes],
+        cis: Optional[list],
+        failed: Any = None,
+        exceptions: Optional[dict] = None,
+        items: Optional[dict] = None,
+    ) -> None:
+        """One body for both roads: the lane's clean tuple (the first eight
+        arguments) and the decoded dict of any other chunk_done."""
         from .calls import GENERIC_STATUS_FAILURE, GENERIC_STATUS_SUCCESS
 
-        handle.inflight.pop(msg["token"], None)
-        fid = msg.get("function_id")
-        count = msg.get("count", 0)
+        handle.inflight.pop(token, None)
+        lane_owned = self._lane_groups.pop(token, None) is not None
         if fid:
             handle.outstanding[fid] = max(handle.outstanding.get(fid, 0) - count, 0)
-        record = self.scheduler.calls.get(msg["call_id"])
+        if not lane_owned or self.pending.get(fid):
+            # the lane has refilled already; per-item inputs of this
+            # function wait on the credit in _dispatch_once
+            self._dispatch_wake.set()
+        record = self.scheduler.calls.get(call_id)
         if record is None:
             return
-        group = record.chunk_groups.get(msg["chunk_id"])
+        group = record.chunk_groups.get(chunk_id)
         if group is None or group.state == "done":
             return
-        if msg.get("failed"):
+        if failed:
             # worker-side setup failure (e.g. missing def): internal requeue
             group.internal_failures += 1
             if group.internal_failures <= MAX_INTERNAL_FAILURE_COUNT and not record.cancelled:
@@ -842,7 +1165,7 @@ class WorkerPool:
             return
         # per-item exceptions materialize real records (the per-item FSM owns
         # retries from here)
-        for ci_s, (data, repr_s) in (msg.get("exceptions") or {}).items():
+        for ci_s, (exc_data, repr_s) in (exceptions or {}).items():
             ci = int(ci_s)
             rec = record.materialize_chunk_item(group, ci)
             self.scheduler.on_worker_output(
@@ -850,12 +1173,12 @@ class WorkerPool:
                 idx=rec.idx,
                 retry_count=rec.retry_count,
                 status=GENERIC_STATUS_FAILURE,
-                output=data,
+                output=exc_data,
                 output_format=1,
                 exc_repr=repr_s,
             )
         # per-item success payloads (tensor/oversized fallback)
-        for ci_s, data in (msg.get("items") or {}).items():
+        for ci_s, item_data in (items or {}).items():
             ci = int(ci_s)
             rec = record.materialize_chunk_item(group, ci)
             self.scheduler.on_worker_output(
@@ -863,12 +1186,11 @@ class WorkerPool:
                 idx=rec.idx,
                 retry_count=rec.retry_count,
                 status=GENERIC_STATUS_SUCCESS,
-                output=data,
+                output=item_data,
                 output_format=1,
                 exc_repr=None,
             )
-        cis = msg.get("cis")  # None => all count items succeeded in order
-        data = msg.get("data")
+        # cis None => all count items succeeded in order
         if data is not None:
             slot = self.scheduler.register_out_chunk(data, count if cis is None else len(cis))
             record.complete_chunk_success(group, cis, slot)
@@ -878,7 +1200,6 @@ class WorkerPool:
         else:
             group.state = "done"
             record._check_done()
-        self._dispatch_wake.set()
 
     async def dispatch_gang(self, fdef: FunctionDef, recs: list) -> None:
         """Place a gang on len(recs) distinct workers at once, bypassing the
@@ -910,6 +1231,11 @@ class WorkerPool:
         """Propagate cancellation to workers holding these inputs
         (parity: server-pushed cancellation via heartbeats,
         reference container_io_manager.py:645-710)."""
+        if self._lane is not None:
+            # queued chunks are dropped; those in flight get the cancel frame
+            for token in self._lane.cancel([t for t in tokens if t in self._lane_groups]):
+                # no chunk_done will come for a chunk that never left the queue
+                self._lane_groups.pop(token, None)
         by_worker: dict[int, list[str]] = {}
         for w in self.workers.values():
             hit = [t for t in tokens if t in w.inflight]
