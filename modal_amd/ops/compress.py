@@ -9,22 +9,35 @@ Container layout (little-endian):
 
 Each segment is a standard LZ4 block, so any LZ4 block decoder can read the
 payload; the CPU reference codec (utils/lz4ref.py) serves GPU-less readers.
+
+Everything that touches the format lives here once:
+
+  ``validate_container``   the only parser; bounds all a decoder indexes with
+  ``compress_spans_gpu``   the only device encoder: LZ4 kernel per span, then
+                           the plan/assemble kernels (csrc/malz.hip) finish
+                           the containers in HBM and one dense D2H fetches them
+  ``decompress_run_gpu``   the only device decoder launch
+
+``compress_buffer_gpu``/``compress_buffers_gpu`` (blobs) and ops/devcodec.py
+(snapshots) are thin callers of these, so their containers are byte-identical
+by construction and the CAS dedups between them.
 """
 
 from __future__ import annotations
 
 import struct
-from typing import Optional
+from typing import Any, Optional, Sequence
 
 from . import gpu_available, load_lib
 
 MAGIC = b"MALZ41"
+HEADER_FIXED = len(MAGIC) + 12  # magic + u64 raw_len + u32 n_seg
 SEG_SIZE = 4096
 OUT_STRIDE = SEG_SIZE + 256
 MIN_GAIN = 0.95  # store raw unless compression saves >=5%
 
 
-def _header(raw_len: int, comp_lens: list[int]) -> bytes:
+def _header(raw_len: int, comp_lens: Sequence[int]) -> bytes:
     return (
         MAGIC
         + struct.pack("<QI", raw_len, len(comp_lens))
@@ -32,14 +45,61 @@ def _header(raw_len: int, comp_lens: list[int]) -> bytes:
     )
 
 
+def worth_keeping(payload_len: Any, raw_len: Any) -> Any:
+    """THE keep/raw rule: a container is kept only when its payload saves
+    at least 1 - MIN_GAIN of the raw bytes (scalars or numpy arrays)."""
+    return payload_len < raw_len * MIN_GAIN
+
+
+def effective_lens(comp_lens: Any, raw_len: int) -> Any:
+    """Bytes every segment takes in the payload (int64 array): its comp_len,
+    or the raw segment length where comp_len is 0."""
+    import numpy as np
+
+    comp_lens = np.asarray(comp_lens)
+    seg_raw = np.full(len(comp_lens), SEG_SIZE, dtype=np.int64)
+    if len(comp_lens):
+        seg_raw[-1] = raw_len - (len(comp_lens) - 1) * SEG_SIZE
+    return np.where(comp_lens == 0, seg_raw, comp_lens.astype(np.int64))
+
+
+def validate_container(
+    blob: bytes, raw_len: Optional[int] = None, what: str = "container"
+) -> tuple[int, Any, int]:
+    """Parse a container and bound everything a decoder will index with:
+    magic, raw_len against the caller's (when given), n_seg against raw_len,
+    every comp_len < SEG_SIZE, header + payload == len(blob). Returns
+    (raw_len, comp_lens int32 array, payload offset); raises ValueError
+    naming ``what``."""
+    import numpy as np
+
+    def bad(why: str) -> ValueError:
+        return ValueError(f"{what}: {why}")
+
+    n = len(blob)
+    if n < HEADER_FIXED or bytes(blob[: len(MAGIC)]) != MAGIC:
+        raise bad("not a MALZ41 container")
+    hdr_raw, n_seg = struct.unpack_from("<QI", blob, len(MAGIC))
+    if raw_len is not None and hdr_raw != raw_len:
+        raise bad(f"container raw_len {hdr_raw} != manifest {raw_len}")
+    if n_seg != -(-hdr_raw // SEG_SIZE):
+        raise bad(f"container has {n_seg} segments for {hdr_raw} bytes")
+    off = HEADER_FIXED + 4 * n_seg
+    if n < off:
+        raise bad("container truncated inside its segment table")
+    comp_lens = np.frombuffer(blob, dtype="<u4", count=n_seg, offset=HEADER_FIXED)
+    if n_seg and int(comp_lens.max()) >= SEG_SIZE:
+        raise bad("segment comp_len out of range")
+    payload = int(effective_lens(comp_lens, hdr_raw).sum())
+    if off + payload != n:
+        raise bad(f"container is {n} bytes, header says {off + payload}")
+    return hdr_raw, comp_lens.astype(np.int32), off
+
+
 def parse_header(blob: bytes) -> tuple[int, list[int], int]:
-    """Returns (raw_len, comp_lens, payload_offset)."""
-    if not blob.startswith(MAGIC):
-        raise ValueError("not a MALZ41 container")
-    raw_len, n_seg = struct.unpack_from("<QI", blob, len(MAGIC))
-    off = len(MAGIC) + 12
-    comp_lens = list(struct.unpack_from(f"<{n_seg}I", blob, off))
-    return raw_len, comp_lens, off + 4 * n_seg
+    """Returns (raw_len, comp_lens, payload_offset) of a valid container."""
+    raw_len, comp_lens, off = validate_container(blob)
+    return raw_len, comp_lens.tolist(), off
 
 
 def is_compressed(blob: bytes) -> bool:
@@ -80,21 +140,18 @@ def compress_buffer_cpu(data: bytes) -> Optional[bytes]:
         else:
             comp_lens.append(0)
             payload += seg
-    if not comp_lens:
-        return None
-    total = len(payload)
-    if total >= n * MIN_GAIN:
+    if not comp_lens or not worth_keeping(len(payload), n):
         return None
     return _header(n, comp_lens) + bytes(payload)
 
 
 def decompress_buffer_cpu(blob: bytes) -> bytes:
+    raw_len, comp_lens, off = validate_container(blob)
     core = _native_core()
     if core is not None:
         return core.malz_decompress(bytes(blob))
     from ..utils import lz4ref
 
-    raw_len, comp_lens, off = parse_header(blob)
     out = bytearray()
     pos = off
     for i, clen in enumerate(comp_lens):
@@ -113,143 +170,141 @@ def decompress_buffer_cpu(blob: bytes) -> bytes:
 # ---------------------------------------------------------------------------
 
 
-def compress_buffer_gpu(data: bytes) -> Optional[bytes]:
-    lib = load_lib(required=True)
+def _check(rc: int, what: str) -> None:
+    if rc != 0:
+        raise RuntimeError(f"{what} failed: hipError {rc}")
+
+
+def _to_dev(arr: Any) -> Any:
+    import numpy as np
     import torch
 
-    n = len(data)
-    n_seg = (n + SEG_SIZE - 1) // SEG_SIZE
-    if n_seg == 0:
+    return torch.from_numpy(np.ascontiguousarray(arr)).cuda()
+
+
+class Workspace:
+    """Device buffers of one ``compress_spans_gpu`` call: the strided LZ4
+    output (OUT_STRIDE per segment), comp_lens and seg_off per segment, and
+    the dense containers."""
+
+    def __init__(self, n_seg: int, dense_bytes: int) -> None:
+        import torch
+
+        self.n_seg = n_seg
+        self.stride = torch.empty(n_seg * OUT_STRIDE, dtype=torch.uint8, device="cuda")
+        self.dense = torch.empty(dense_bytes, dtype=torch.uint8, device="cuda")
+        self.comp_lens = torch.empty(n_seg, dtype=torch.int32, device="cuda")
+        self.seg_off = torch.empty(n_seg, dtype=torch.int64, device="cuda")
+
+    @classmethod
+    def for_lengths(cls, raw_lens: Sequence[int]) -> "Workspace":
+        """Sized to one call: every span kept would still fit the dense part."""
+        n_seg = sum(-(-n // SEG_SIZE) for n in raw_lens)
+        return cls(n_seg, len(raw_lens) * HEADER_FIXED + 4 * n_seg + sum(raw_lens))
+
+
+def compress_spans_gpu(
+    lib: Any, base: int, spans: Sequence[tuple[int, int]], ws: Workspace
+) -> list:
+    """Containers of the device bytes ``(base + offset, raw_len)`` per span,
+    None where compression does not pay. One LZ4 launch per span, one plan
+    launch, ONE sync (the per-span payload totals), one assemble launch and
+    one D2H of the dense containers, all on the current stream."""
+    import numpy as np
+    import torch
+
+    from .staging import copy_from_device
+
+    out: list = [None] * len(spans)
+    if not spans:
+        return out
+    stream = torch.cuda.current_stream().cuda_stream
+    first_seg, n_segs, sb = [], [], 0
+    for off, ln in spans:
+        n_seg = -(-ln // SEG_SIZE)
+        if sb + n_seg > ws.n_seg:
+            raise RuntimeError("compress spans exceed the workspace")
+        _check(
+            lib.ma_lz4_compress(
+                base + off, ln, ws.stride.data_ptr() + sb * OUT_STRIDE,
+                ws.comp_lens.data_ptr() + sb * 4, OUT_STRIDE, n_seg, stream,
+            ),
+            "lz4 compress kernel",
+        )
+        first_seg.append(sb)
+        n_segs.append(n_seg)
+        sb += n_seg
+    raw_lens = np.array([ln for _off, ln in spans], dtype=np.int64)
+    first_d = _to_dev(np.array(first_seg, dtype=np.int32))
+    raw_d = _to_dev(raw_lens)
+    src_off_d = _to_dev(np.array([off for off, _ln in spans], dtype=np.int64))
+    payload_d = torch.empty(len(spans), dtype=torch.int64, device="cuda")
+    _check(
+        lib.ma_malz_plan(
+            ws.comp_lens.data_ptr(), first_d.data_ptr(), raw_d.data_ptr(),
+            ws.seg_off.data_ptr(), payload_d.data_ptr(), len(spans), stream,
+        ),
+        "malz plan kernel",
+    )
+    totals = payload_d.cpu().numpy()  # the one sync
+    keep = worth_keeping(totals, raw_lens)
+    sizes = np.where(keep, HEADER_FIXED + 4 * np.array(n_segs, dtype=np.int64) + totals, 0)
+    ends = np.cumsum(sizes)
+    out_off = np.where(keep, ends - sizes, -1)  # -1: the kernel skips the span
+    dense_len = int(ends[-1])
+    if dense_len == 0:
+        return out
+    if dense_len > ws.dense.numel():
+        raise RuntimeError("dense containers exceed the workspace")
+    out_off_d = _to_dev(out_off)
+    _check(
+        lib.ma_malz_assemble(
+            base, src_off_d.data_ptr(), ws.stride.data_ptr(), OUT_STRIDE,
+            ws.comp_lens.data_ptr(), ws.seg_off.data_ptr(), first_d.data_ptr(),
+            raw_d.data_ptr(), ws.dense.data_ptr(), out_off_d.data_ptr(),
+            len(spans), stream,
+        ),
+        "malz assemble kernel",
+    )
+    dense = copy_from_device(ws.dense.data_ptr(), dense_len)
+    for j in np.flatnonzero(keep):
+        out[j] = dense[out_off[j] : out_off[j] + sizes[j]]
+    return out
+
+
+def compress_buffer_gpu(data: bytes) -> Optional[bytes]:
+    if len(data) == 0:
         return None
+    lib = load_lib(required=True)
     from .staging import stage_to_gpu
 
     src = stage_to_gpu(data)
-    stride_buf = torch.empty(n_seg * OUT_STRIDE, dtype=torch.uint8, device="cuda")
-    comp_lens_d = torch.zeros(n_seg, dtype=torch.int32, device="cuda")
-    rc = lib.ma_lz4_compress(
-        src.data_ptr(), n, stride_buf.data_ptr(), comp_lens_d.data_ptr(),
-        OUT_STRIDE, n_seg, torch.cuda.current_stream().cuda_stream,
-    )
-    if rc != 0:
-        raise RuntimeError(f"lz4 compress kernel failed: hipError {rc}")
-    torch.cuda.synchronize()
-    comp_lens = comp_lens_d.cpu().tolist()
-    eff_lens = []
-    total = 0
-    for i, clen in enumerate(comp_lens):
-        seg_raw = min(SEG_SIZE, n - i * SEG_SIZE)
-        eff = clen if clen else seg_raw
-        eff_lens.append(eff)
-        total += eff
-    if total >= n * MIN_GAIN:
-        return None
-    # stage raw segments into their stride slots, then compact with the pack kernel
-    for i, clen in enumerate(comp_lens):
-        if clen == 0:
-            seg_raw = min(SEG_SIZE, n - i * SEG_SIZE)
-            stride_buf[i * OUT_STRIDE : i * OUT_STRIDE + seg_raw] = src[
-                i * SEG_SIZE : i * SEG_SIZE + seg_raw
-            ]
-    from .packing import pack_gpu
-
-    offsets = torch.arange(n_seg, dtype=torch.int64) * OUT_STRIDE
-    packed, _ = pack_gpu(stride_buf, offsets, torch.tensor(eff_lens, dtype=torch.int64))
-    torch.cuda.synchronize()
-    from .staging import fetch_from_gpu
-
-    payload = fetch_from_gpu(packed)
-    return _header(n, comp_lens) + payload
+    ws = Workspace.for_lengths([len(data)])
+    return compress_spans_gpu(lib, src.data_ptr(), [(0, len(data))], ws)[0]
 
 
 def compress_buffers_gpu(buffers: list, staged: "object" = None, only: "object" = None) -> list:
-    """Batched compression: ONE host->device transfer and ONE sync for a
-    whole upload's blocks (volume v2 8 MiB blocks are exact multiples of
-    SEG_SIZE, so per-buffer kernel launches share the staged source at
-    4 KiB-aligned offsets). Per-block round trips previously dominated
-    config-4 upload wall time. Returns per-buffer container bytes or None
-    (incompressible / empty)."""
+    """Batched compression: ONE host->device transfer, ONE sync and ONE
+    readback for a whole upload's blocks. ``staged`` is a
+    ``stage_many_to_gpu`` result shared with the digest pass; ``only`` picks
+    the buffers to compress. Returns per-buffer container bytes or None
+    (incompressible / empty / not picked)."""
     lib = load_lib(required=True)
-    import torch
-
-    pick = set(range(len(buffers))) if only is None else set(only)
-    if staged is not None:
-        src, src_offsets = staged  # shared with the digest pass
-    else:
+    out: list = [None] * len(buffers)
+    pick = sorted(set(range(len(buffers))) if only is None else set(only))
+    pick = [i for i in pick if len(buffers[i])]
+    if not pick:
+        return out
+    if staged is None:
         from .staging import stage_many_to_gpu
 
         # one pinned H2D for all buffers, 4 KiB-aligned (no concat bytearray)
-        src, src_offsets = stage_many_to_gpu(buffers, align=SEG_SIZE)
-    metas = []  # (src_off, n, n_seg, seg_base); n_seg=0 for skipped buffers
-    seg_base = 0
-    for bi, (data, src_off) in enumerate(zip(buffers, src_offsets)):
-        n = len(data)
-        n_seg = (n + SEG_SIZE - 1) // SEG_SIZE if bi in pick else 0
-        metas.append((src_off, n, n_seg, seg_base))
-        seg_base += n_seg
-    total_seg = seg_base
-    if total_seg == 0:
-        return [None] * len(buffers)
-    stride_buf = torch.empty(total_seg * OUT_STRIDE, dtype=torch.uint8, device="cuda")
-    comp_lens_d = torch.zeros(total_seg, dtype=torch.int32, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
-    for src_off, n, n_seg, sb in metas:
-        if n_seg == 0:
-            continue
-        rc = lib.ma_lz4_compress(
-            src.data_ptr() + src_off, n,
-            stride_buf.data_ptr() + sb * OUT_STRIDE,
-            comp_lens_d.data_ptr() + sb * 4,
-            OUT_STRIDE, n_seg, stream,
-        )
-        if rc != 0:
-            raise RuntimeError(f"lz4 compress kernel failed: hipError {rc}")
-    torch.cuda.synchronize()
-    comp_lens_all = comp_lens_d.cpu().tolist()  # one D2H
-
-    from .packing import pack_gpu
-    from .staging import fetch_from_gpu
-
-    # decide per buffer, then compact EVERY kept buffer's segments with ONE
-    # pack launch and ONE pinned D2H (a per-buffer pack+sync+readback loop
-    # was 6x the kernel time in the config-4 trace)
-    kept: list = []  # (meta, comp_lens, eff_lens, total)
-    out: list = [None] * len(buffers)
-    for bi, (src_off, n, n_seg, sb) in enumerate(metas):
-        if n_seg == 0:
-            continue
-        comp_lens = comp_lens_all[sb : sb + n_seg]
-        eff_lens, total = [], 0
-        for i, clen in enumerate(comp_lens):
-            seg_raw = min(SEG_SIZE, n - i * SEG_SIZE)
-            eff = clen if clen else seg_raw
-            eff_lens.append(eff)
-            total += eff
-        if total >= n * MIN_GAIN:
-            continue
-        for i, clen in enumerate(comp_lens):
-            if clen == 0:
-                seg_raw = min(SEG_SIZE, n - i * SEG_SIZE)
-                dst0 = (sb + i) * OUT_STRIDE
-                src0 = src_off + i * SEG_SIZE
-                stride_buf[dst0 : dst0 + seg_raw] = src[src0 : src0 + seg_raw]
-        kept.append((bi, n, sb, n_seg, comp_lens, eff_lens, total))
-    if not kept:
-        return out
-    all_offsets = torch.cat(
-        [(torch.arange(n_seg, dtype=torch.int64) + sb) * OUT_STRIDE
-         for _bi, _n, sb, n_seg, _cl, _el, _t in kept]
-    )
-    all_eff = torch.tensor(
-        [e for _bi, _n, _sb, _ns, _cl, eff_lens, _t in kept for e in eff_lens],
-        dtype=torch.int64,
-    )
-    packed, _ = pack_gpu(stride_buf, all_offsets, all_eff)
-    torch.cuda.synchronize()
-    payload_all = fetch_from_gpu(packed)
-    pos = 0
-    for bi, n, _sb, _ns, comp_lens, _eff_lens, total in kept:
-        out[bi] = _header(n, comp_lens) + payload_all[pos : pos + total]
-        pos += total
+        staged = stage_many_to_gpu(buffers, align=SEG_SIZE)
+    src, src_offsets = staged
+    spans = [(src_offsets[i], len(buffers[i])) for i in pick]
+    ws = Workspace.for_lengths([n for _off, n in spans])
+    for i, container in zip(pick, compress_spans_gpu(lib, src.data_ptr(), spans, ws)):
+        out[i] = container
     return out
 
 
@@ -261,38 +316,52 @@ def compress_buffers(buffers: list, staged: "object" = None, only: "object" = No
     return [None] * len(buffers)
 
 
+def decompress_run_gpu(
+    lib: Any, comp: int, headers: Sequence[tuple[int, Sequence[int]]], dst: int
+) -> int:
+    """Decompress a run of VALIDATED containers, ``headers`` their
+    ``(raw_len, comp_lens)``, whose payloads lie back to back at device
+    pointer ``comp`` and whose raw bytes are consecutive at ``dst``, on the
+    current stream. Returns 0, or 1 + the run's first segment found corrupt;
+    the stream has drained either way."""
+    import numpy as np
+    import torch
+
+    comp_lens = np.concatenate([np.asarray(cl, dtype=np.int32) for _n, cl in headers])
+    eff = np.concatenate([effective_lens(cl, n) for n, cl in headers])
+    comp_offs = np.cumsum(eff)
+    comp_offs -= eff  # exclusive
+    offs_d = _to_dev(comp_offs)
+    lens_d = _to_dev(comp_lens)
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    _check(
+        lib.ma_lz4_decompress(
+            comp, offs_d.data_ptr(), lens_d.data_ptr(), dst,
+            sum(n for n, _cl in headers), status.data_ptr(), len(comp_lens),
+            torch.cuda.current_stream().cuda_stream,
+        ),
+        "lz4 decompress kernel",
+    )
+    return int(status.item())  # syncs: the tables may be freed
+
+
+def corrupt_message(status: int) -> str:
+    return f"LZ4 container corrupt at segment {status - 1}"
+
+
 def decompress_buffer_gpu(blob: bytes) -> bytes:
+    raw_len, comp_lens, off = validate_container(blob)  # before any launch
     lib = load_lib(required=True)
     import torch
 
-    raw_len, comp_lens, off = parse_header(blob)
-    n_seg = len(comp_lens)
-    from .staging import stage_to_gpu
+    from .staging import fetch_from_gpu, stage_to_gpu
 
-    payload = stage_to_gpu(blob[off:])
-    offs = []
-    pos = 0
-    for i, clen in enumerate(comp_lens):
-        offs.append(pos)
-        pos += clen if clen else min(SEG_SIZE, raw_len - i * SEG_SIZE)
-    comp_offs = torch.tensor(offs, dtype=torch.int64).cuda()
-    comp_lens_d = torch.tensor(comp_lens, dtype=torch.int32).cuda()
-    dst = torch.empty(max(raw_len, 1), dtype=torch.uint8, device="cuda")
-    status = torch.zeros(1, dtype=torch.int32, device="cuda")
-    rc = lib.ma_lz4_decompress(
-        payload.data_ptr(), comp_offs.data_ptr(), comp_lens_d.data_ptr(),
-        dst.data_ptr(), raw_len, status.data_ptr(), n_seg,
-        torch.cuda.current_stream().cuda_stream,
-    )
-    if rc != 0:
-        raise RuntimeError(f"lz4 decompress kernel failed: hipError {rc}")
-    torch.cuda.synchronize()
-    bad = int(status.item())
+    comp = stage_to_gpu(memoryview(blob)[off:])
+    dst = torch.empty(raw_len, dtype=torch.uint8, device="cuda")
+    bad = decompress_run_gpu(lib, comp.data_ptr(), [(raw_len, comp_lens)], dst.data_ptr())
     if bad:
-        raise ValueError(f"LZ4 container corrupt at segment {bad - 1}")
-    from .staging import fetch_from_gpu
-
-    return fetch_from_gpu(dst[:raw_len])
+        raise ValueError(corrupt_message(bad))
+    return fetch_from_gpu(dst)
 
 
 # ---------------------------------------------------------------------------

@@ -1,10 +1,12 @@
 // MALZ41 container assembly on the device for gfx950 (MI355X, CDNA4).
 //
 // The LZ4 kernel (lz4.hip) leaves every 4 KiB segment's block in a fixed-
-// stride slot plus a comp_len per segment. Finishing the container (layout in
-// ops/compress.py) used to mean reading the whole strided buffer back and
-// compacting on the host. These two kernels do it where the data lives, for a
-// batch of blocks at once, so the only large D2H is the dense container:
+// stride slot plus a comp_len per segment. These two kernels finish the
+// container (layout in ops/compress.py) where the data lives, for a batch of
+// blocks at once, so the only large D2H is the dense container. They are the
+// one device encoder, compress.compress_spans_gpu, behind blobs and snapshots
+// alike; only the streamed upload pipeline (ops/pipeline.py) still reads the
+// whole strided buffer back and compacts on the host.
 //
 //   plan      per block: eff[i] = comp_len ? comp_len : raw segment length,
 //             exclusive scan -> seg_off, sum -> blk_payload (the host's
@@ -15,6 +17,8 @@
 //
 // Segment arrays (comp_lens, seg_off, stride slots) are indexed by
 // blk_first_seg[b] + s; a block's segment count is ceil(blk_raw_len[b]/4096).
+// seg_off is int64: a block is a whole blob on the BlobStore.put path, with
+// no bound on its size.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,7 +42,7 @@ extern "C" __global__ __launch_bounds__(PLAN_BLOCK) void malz_plan_kernel(
     const int32_t* __restrict__ comp_lens,
     const int32_t* __restrict__ blk_first_seg,
     const int64_t* __restrict__ blk_raw_len,
-    int32_t* __restrict__ seg_off,
+    int64_t* __restrict__ seg_off,
     int64_t* __restrict__ blk_payload) {
   __shared__ int64_t wave_sum[PLAN_BLOCK / WAVE];
   const int b = blockIdx.x;
@@ -48,7 +52,7 @@ extern "C" __global__ __launch_bounds__(PLAN_BLOCK) void malz_plan_kernel(
   const int64_t raw_len = blk_raw_len[b];
   const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
   const int32_t* cl = comp_lens + blk_first_seg[b];
-  int32_t* so = seg_off + blk_first_seg[b];
+  int64_t* so = seg_off + blk_first_seg[b];
 
   // each thread owns a run of consecutive segments (8 for an 8 MiB block)
   const int64_t per = (n_seg + PLAN_BLOCK - 1) / PLAN_BLOCK;
@@ -74,7 +78,7 @@ extern "C" __global__ __launch_bounds__(PLAN_BLOCK) void malz_plan_kernel(
   }
   int64_t run = base + incl - mine;
   for (int64_t s = lo; s < hi; ++s) {
-    so[s] = (int32_t)run;
+    so[s] = run;
     run += seg_eff(cl[s], raw_len, s);
   }
   if (tid == 0) blk_payload[b] = total;
@@ -135,7 +139,7 @@ extern "C" __global__ __launch_bounds__(ASM_BLOCK) void malz_assemble_kernel(
     const int64_t* __restrict__ blk_src_off,
     const uint8_t* __restrict__ stride_buf, int out_stride,
     const int32_t* __restrict__ comp_lens,
-    const int32_t* __restrict__ seg_off,
+    const int64_t* __restrict__ seg_off,
     const int32_t* __restrict__ blk_first_seg,
     const int64_t* __restrict__ blk_raw_len,
     uint8_t* __restrict__ out,
@@ -177,7 +181,7 @@ extern "C" int ma_malz_plan(const void* comp_lens, const void* blk_first_seg,
   hipLaunchKernelGGL(malz_plan_kernel, dim3(n_blocks), dim3(PLAN_BLOCK), 0,
                      (hipStream_t)stream, (const int32_t*)comp_lens,
                      (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
-                     (int32_t*)seg_off, (int64_t*)blk_payload);
+                     (int64_t*)seg_off, (int64_t*)blk_payload);
   return (int)hipGetLastError();
 }
 
@@ -192,7 +196,7 @@ extern "C" int ma_malz_assemble(const void* src, const void* blk_src_off,
     hipLaunchKernelGGL(malz_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
                        (hipStream_t)stream, (const uint8_t*)src,
                        (const int64_t*)blk_src_off, (const uint8_t*)stride_buf, out_stride,
-                       (const int32_t*)comp_lens, (const int32_t*)seg_off,
+                       (const int32_t*)comp_lens, (const int64_t*)seg_off,
                        (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
                        (uint8_t*)out, (const int64_t*)blk_out_off, base);
     hipError_t err = hipGetLastError();

@@ -18,7 +18,7 @@ from __future__ import annotations
 
 import hashlib
 import struct
-from typing import Optional, Union
+from typing import Any, Optional, Sequence, Union
 
 from . import gpu_available, load_lib
 
@@ -49,31 +49,65 @@ def tree_sha256_cpu(data: Buffer) -> bytes:
     return _root_digest(len(data), bytes(digests))
 
 
-def _tree_sha256_gpu(data: Buffer) -> Optional[bytes]:
-    lib = load_lib(required=True)
+def leaf_table(spans: Sequence[tuple[int, int]]) -> tuple:
+    """The tree hash's leaves for buffers ``[(base_offset, length)]`` laid
+    out in one address space: (offsets int64, lengths int64, leaves per
+    span), span after span, every leaf LEAF_SIZE long but a span's last."""
+    import numpy as np
+
+    base = np.array([off for off, _n in spans], dtype=np.int64)
+    size = np.array([n for _off, n in spans], dtype=np.int64)
+    counts = -(-size // LEAF_SIZE)
+    # offset of every leaf inside its span: 0, LEAF_SIZE, ... per span. All
+    # in place: `temporary - x` on arrays this size makes numpy look for an
+    # elidable temporary with backtrace(), whose first call in a process
+    # that has torch loaded costs 0.1-0.3 s
+    within = np.arange(int(counts.sum()), dtype=np.int64)
+    within -= np.repeat(np.cumsum(counts) - counts, counts)
+    within *= LEAF_SIZE
+    offsets = np.repeat(base, counts)
+    offsets += within
+    lengths = np.repeat(size, counts)
+    lengths -= within
+    np.minimum(lengths, LEAF_SIZE, out=lengths)
+    return offsets, lengths, counts
+
+
+def tree_roots(spans: Sequence[tuple[int, int]], counts: Any, leaf_digests: bytes) -> list[bytes]:
+    """Root digests of the spans of a ``leaf_table`` from its leaves' digests."""
+    roots, first = [], 0
+    for (_off, n), n_leaves in zip(spans, counts):
+        roots.append(_root_digest(n, leaf_digests[first * 32 : (first + int(n_leaves)) * 32]))
+        first += int(n_leaves)
+    return roots
+
+
+def sha256_leaves_gpu(lib: Any, base: int, offsets: Any, lengths: Any) -> Any:
+    """One ma_sha256_many over (base + offsets[i], lengths[i]), numpy int64
+    tables, on the current stream; [n, 32] uint8 on the host."""
     import torch
 
-    n = len(data)
-    n_leaves = (n + LEAF_SIZE - 1) // LEAF_SIZE
-    from .staging import stage_to_gpu
-
-    src = stage_to_gpu(data)  # pinned arena + side-stream hipMemcpyAsync
-    offsets = torch.arange(0, n_leaves, dtype=torch.int64) * LEAF_SIZE
-    lengths = torch.full((n_leaves,), LEAF_SIZE, dtype=torch.int64)
-    if n % LEAF_SIZE:
-        lengths[-1] = n % LEAF_SIZE
-    offsets_d = offsets.cuda()
-    lengths_d = lengths.cuda()
-    out = torch.empty((n_leaves, 32), dtype=torch.uint8, device="cuda")
-    stream = torch.cuda.current_stream().cuda_stream
+    n = len(offsets)
+    off_d = torch.from_numpy(offsets).cuda()
+    len_d = torch.from_numpy(lengths).cuda()
+    out = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
     rc = lib.ma_sha256_many(
-        src.data_ptr(), offsets_d.data_ptr(), lengths_d.data_ptr(), out.data_ptr(),
-        n_leaves, stream,
+        base, off_d.data_ptr(), len_d.data_ptr(), out.data_ptr(), n,
+        torch.cuda.current_stream().cuda_stream,
     )
     if rc != 0:
         raise RuntimeError(f"sha256 kernel failed: hipError {rc}")
-    torch.cuda.synchronize()
-    return _root_digest(n, out.cpu().numpy().tobytes())
+    return out.cpu().numpy()
+
+
+def _tree_sha256_gpu(data: Buffer) -> Optional[bytes]:
+    lib = load_lib(required=True)
+    from .staging import stage_to_gpu
+
+    src = stage_to_gpu(data)  # pinned arena + side-stream hipMemcpyAsync
+    offsets, lengths, _counts = leaf_table([(0, len(data))])
+    leaves = sha256_leaves_gpu(lib, src.data_ptr(), offsets, lengths)
+    return _root_digest(len(data), leaves.tobytes())
 
 
 def sha256_many_gpu(
@@ -123,74 +157,39 @@ def content_digests_batch(
     if total < gpu_threshold or not gpu_available():
         return [content_digest(b, gpu_threshold) for b in buffers]
     lib = load_lib(required=True)
-    import torch
-
-    spans: list[tuple[int, int]] = []  # (first_leaf_index, n_leaves) per buffer
-    offsets: list[int] = []
-    lengths: list[int] = []
-    small_idx: dict[int, str] = {}
-    big_bufs: list = []
-    big_meta: list[int] = []  # index into spans to fix up with real offsets
-    for i, data in enumerate(buffers):
-        if len(data) < gpu_threshold:
-            # digest form must depend only on the buffer's own size so every
-            # path (single, batch, CPU, GPU) computes the same CAS key
-            import hashlib as _hl
-
-            small_idx[i] = _hl.sha256(bytes(data)).hexdigest()
-            spans.append((len(offsets), 0))
-            continue
-        n_leaves = (len(data) + LEAF_SIZE - 1) // LEAF_SIZE
-        spans.append((len(offsets), n_leaves))
-        big_meta.append((len(big_bufs), i, len(offsets), n_leaves))
-        big_bufs.append(data)
-        offsets.extend([0] * n_leaves)  # placeholders until staged
-        for leaf in range(n_leaves):
-            lengths.append(min(LEAF_SIZE, len(data) - leaf * LEAF_SIZE))
-    if not lengths:
-        return [small_idx[i] for i in range(len(buffers))]
+    # digest form must depend only on the buffer's own size so every path
+    # (single, batch, CPU, GPU) computes the same CAS key
+    results: list = [
+        content_digest(b, gpu_threshold) if len(b) < gpu_threshold else None for b in buffers
+    ]
+    big = [i for i, d in enumerate(results) if d is None]
+    if not big:
+        return results
     if staged is not None:
         # caller pre-staged ALL buffers (one pinned H2D shared with the
-        # compression pass, blobs.put_many); map big-buffer offsets from it
+        # compression pass, blobs.put_many)
         src, all_offsets = staged
-        base_offsets = [all_offsets[i] for _bk, i, _f, _n in big_meta]
+        bases = [all_offsets[i] for i in big]
     else:
         from .staging import stage_many_to_gpu
 
         # one pinned H2D for all large buffers (no concat bytearray pass)
-        src, base_offsets = stage_many_to_gpu(big_bufs, align=LEAF_SIZE)
-    for (bk, _i, first, n_leaves), base in zip(big_meta, base_offsets):
-        for leaf in range(n_leaves):
-            offsets[first + leaf] = base + leaf * LEAF_SIZE
-    out = torch.empty((len(offsets), 32), dtype=torch.uint8, device="cuda")
-    off_d = torch.tensor(offsets, dtype=torch.int64).cuda()
-    len_d = torch.tensor(lengths, dtype=torch.int64).cuda()
-    rc = lib.ma_sha256_many(
-        src.data_ptr(), off_d.data_ptr(), len_d.data_ptr(), out.data_ptr(),
-        len(offsets), torch.cuda.current_stream().cuda_stream,
-    )
-    if rc != 0:
-        raise RuntimeError(f"sha256 kernel failed: hipError {rc}")
-    torch.cuda.synchronize()
-    leaf_digests = out.cpu().numpy().tobytes()
-    results: list[str] = []
-    for i, data in enumerate(buffers):
-        if i in small_idx:
-            results.append(small_idx[i])
-        else:
-            first, n_leaves = spans[i]
-            results.append(
-                _root_digest(len(data), leaf_digests[first * 32 : (first + n_leaves) * 32]).hex()
-            )
+        src, bases = stage_many_to_gpu([buffers[i] for i in big], align=LEAF_SIZE)
+    spans = [(base, len(buffers[i])) for base, i in zip(bases, big)]
+    offsets, lengths, counts = leaf_table(spans)
+    leaves = sha256_leaves_gpu(lib, src.data_ptr(), offsets, lengths)
+    for i, root in zip(big, tree_roots(spans, counts, leaves.tobytes())):
+        results[i] = root.hex()
     return results
 
 
-def content_digest(data: Buffer, gpu_threshold: int = GPU_MIN_BYTES) -> str:
+def content_digest(data: Buffer, gpu_threshold: int = GPU_MIN_BYTES, *, gpu: bool = True) -> str:
     """The CAS key: plain SHA-256 below the threshold, tree digest above.
 
     Deterministic for a given payload size, so every process computes the
-    same key regardless of whether it has a GPU.
+    same key regardless of whether it has a GPU; ``gpu=False`` keeps the
+    tree hash on the host whatever the machine has.
     """
     if len(data) < gpu_threshold:
         return hashlib.sha256(data).hexdigest()
-    return tree_sha256(data).hex()
+    return (tree_sha256(data) if gpu else tree_sha256_cpu(data)).hex()

@@ -20,12 +20,12 @@ compress.compress_buffer): same tree digests, same MALZ41 containers.
 
 from __future__ import annotations
 
-import struct
+import hashlib
 from concurrent.futures import ThreadPoolExecutor
 from typing import Any, Callable, Optional
 
-from .compress import MAGIC, MIN_GAIN, OUT_STRIDE, SEG_SIZE
-from .hashing import GPU_MIN_BYTES, LEAF_SIZE, _root_digest
+from .compress import OUT_STRIDE, SEG_SIZE, _header, effective_lens, worth_keeping
+from .hashing import GPU_MIN_BYTES, LEAF_SIZE, _root_digest, leaf_table
 
 WINDOW_BYTES = 64 * 1024 * 1024
 
@@ -143,23 +143,11 @@ def hash_compress_blocks(
         main = torch.cuda.current_stream()
         main.wait_event(slot.ev_h2d)
         # --- digest: one sha256 dispatch over every leaf of the window ---
-        leaf_offs: list[int] = []
-        leaf_lens: list[int] = []
-        spans = []  # (first_leaf, n_leaves) per block
-        for i, off in zip(win, offs):
-            n = len(blocks[i])
-            n_leaves = (n + LEAF_SIZE - 1) // LEAF_SIZE
-            spans.append((len(leaf_offs), n_leaves))
-            for leaf in range(n_leaves):
-                leaf_offs.append(off + leaf * LEAF_SIZE)
-                leaf_lens.append(min(LEAF_SIZE, n - leaf * LEAF_SIZE))
+        spans = [(off, len(blocks[i])) for i, off in zip(win, offs)]
+        leaf_offs, leaf_lens, counts = leaf_table(spans)
         n_leaf = len(leaf_offs)
-        slot.off_leaf[:n_leaf].copy_(
-            torch.tensor(leaf_offs, dtype=torch.int64), non_blocking=True
-        )
-        slot.len_leaf[:n_leaf].copy_(
-            torch.tensor(leaf_lens, dtype=torch.int64), non_blocking=True
-        )
+        slot.off_leaf[:n_leaf].copy_(torch.from_numpy(leaf_offs), non_blocking=True)
+        slot.len_leaf[:n_leaf].copy_(torch.from_numpy(leaf_lens), non_blocking=True)
         rc = lib.ma_sha256_many(
             slot.dev.data_ptr(), slot.off_leaf.data_ptr(), slot.len_leaf.data_ptr(),
             slot.digests.data_ptr(), n_leaf, main.cuda_stream,
@@ -201,51 +189,36 @@ def hash_compress_blocks(
                     slot.stride[: seg_base * OUT_STRIDE], non_blocking=True
                 )
             slot.ev_d2h.record(d2h)
-        slot.meta = (win, offs, spans, seg_meta, n_leaf)
+        first_leaf = [0, *np.cumsum(counts).tolist()]  # block k: [k] .. [k + 1]
+        slot.meta = (win, offs, first_leaf, seg_meta, n_leaf)
 
     def assemble(slot: _Slot) -> None:
         """After ev_d2h: build digests + containers on a worker thread."""
-        win, offs, spans, seg_meta, n_leaf = slot.meta
+        win, offs, first_leaf, seg_meta, n_leaf = slot.meta
         leaf_bytes = slot.out_digests[: n_leaf * 32].numpy().tobytes()
         lens_np = slot.out_lens.numpy()
         payload_np = slot.out_payload.numpy()
         for k, (i, off) in enumerate(zip(win, offs)):
             n = len(blocks[i])
-            first, n_leaves = spans[k]
             if n < GPU_MIN_BYTES:
-                import hashlib
-
                 digest = hashlib.sha256(blocks[i]).hexdigest()
             else:
-                digest = _root_digest(
-                    n, leaf_bytes[first * 32 : (first + n_leaves) * 32]
-                ).hex()
+                digest = _root_digest(n, leaf_bytes[first_leaf[k] * 32 : first_leaf[k + 1] * 32]).hex()
             digests[i] = digest
             container = None
             if compress and seg_meta:
                 seg_base, n_seg = seg_meta[k]
-                comp_lens = lens_np[seg_base : seg_base + n_seg].tolist()
-                eff_total = 0
-                for si, clen in enumerate(comp_lens):
-                    seg_raw = min(SEG_SIZE, n - si * SEG_SIZE)
-                    eff_total += clen if clen else seg_raw
-                if eff_total < n * MIN_GAIN:
-                    parts = [
-                        MAGIC,
-                        struct.pack("<QI", n, n_seg),
-                        struct.pack(f"<{n_seg}I", *comp_lens),
-                    ]
+                comp_lens = lens_np[seg_base : seg_base + n_seg]
+                eff = effective_lens(comp_lens, n)
+                if worth_keeping(int(eff.sum()), n):
+                    parts = [_header(n, comp_lens.tolist())]
                     blk = blocks[i]
-                    for si, clen in enumerate(comp_lens):
+                    for si, (clen, elen) in enumerate(zip(comp_lens.tolist(), eff.tolist())):
                         if clen:
                             s0 = (seg_base + si) * OUT_STRIDE
                             parts.append(payload_np[s0 : s0 + clen].tobytes())
                         else:  # raw segment comes from the HOST copy
-                            parts.append(
-                                bytes(blk[si * SEG_SIZE : si * SEG_SIZE + min(
-                                    SEG_SIZE, n - si * SEG_SIZE
-                                )])
-                            )
+                            parts.append(bytes(blk[si * SEG_SIZE : si * SEG_SIZE + elen]))
                     container = b"".join(parts)
             containers[i] = container
             if store is not None:

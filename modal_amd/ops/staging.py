@@ -5,7 +5,9 @@ hipMemcpyAsync on a dedicated stream instead of pageable copies on the
 default stream (pageable H2D is roughly half pinned bandwidth and
 serializes with compute). One process-wide pinned arena is reused and
 guarded by a lock; callers get an ordinary device tensor synchronized
-with the caller's current stream.
+with the caller's current stream. ``copy_to_device``/``copy_from_device``
+are the pointer-based twins for memory torch does not own (ops/devcodec.py):
+same arena, same lock, the copy on the caller's own stream.
 """
 
 from __future__ import annotations
@@ -20,6 +22,8 @@ _h2d_stream: Any = None
 _d2h_stream: Any = None
 
 _MIN_CAP = 64 * 1024 * 1024
+_MAX_PIN = 1 << 30  # larger payloads are not pinned whole
+_H2D, _D2H = 1, 2  # ma_malz_copy kinds
 
 
 def _ensure(n: int) -> None:
@@ -45,7 +49,7 @@ def stage_to_gpu(data: Any) -> Any:
     n = len(data)
     if n == 0:
         return torch.empty(0, dtype=torch.uint8, device="cuda")
-    if n > (1 << 30):
+    if n > _MAX_PIN:
         return torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
     with _lock:
         _ensure(n)
@@ -76,7 +80,7 @@ def stage_many_to_gpu(buffers: list, align: int = 1) -> tuple:
     total = off
     if total == 0:
         return torch.empty(0, dtype=torch.uint8, device="cuda"), offsets
-    if total > (1 << 30):
+    if total > _MAX_PIN:
         big = bytearray(total)
         for data, o in zip(buffers, offsets):
             big[o : o + len(data)] = data
@@ -100,7 +104,7 @@ def fetch_from_gpu(tensor: Any) -> bytes:
     n = tensor.numel()
     if n == 0:
         return b""
-    if n > (1 << 30):
+    if n > _MAX_PIN:
         return tensor.cpu().numpy().tobytes()
     with _lock:
         _ensure(n)
@@ -109,3 +113,46 @@ def fetch_from_gpu(tensor: Any) -> bytes:
             _pin_buf[:n].copy_(tensor, non_blocking=True)
         _d2h_stream.synchronize()
         return _pin_np[:n].tobytes()
+
+
+def _copy(dst: int, src: int, n: int, kind: int) -> None:
+    """ma_malz_copy on the caller's stream, then wait for it."""
+    import torch
+
+    from . import load_lib
+
+    stream = torch.cuda.current_stream()
+    rc = load_lib(required=True).ma_malz_copy(dst, src, n, kind, stream.cuda_stream)
+    if rc != 0:
+        raise RuntimeError(f"staging copy failed: hipError {rc}")
+    stream.synchronize()  # the arena is reused by the next caller
+
+
+def copy_to_device(dev_ptr: int, parts: Any) -> None:
+    """Host buffers, concatenated -> device memory at ``dev_ptr``, through
+    the pinned arena on the caller's stream."""
+    import numpy as np
+
+    total = sum(len(p) for p in parts)
+    if total == 0:
+        return
+    with _lock:
+        _ensure(total)
+        pos = 0
+        for p in parts:
+            _pin_np[pos : pos + len(p)] = np.frombuffer(p, dtype=np.uint8)
+            pos += len(p)
+        _copy(dev_ptr, _pin_buf.data_ptr(), total, _H2D)
+
+
+def copy_from_device(dev_ptr: int, n: int) -> bytes:
+    """``n`` bytes of device memory at ``dev_ptr`` -> bytes, through the
+    pinned arena on the caller's stream, at most _MAX_PIN at a time."""
+    chunks = []
+    with _lock:
+        for pos in range(0, n, _MAX_PIN):
+            m = min(_MAX_PIN, n - pos)
+            _ensure(m)
+            _copy(_pin_buf.data_ptr(), dev_ptr + pos, m, _D2H)
+            chunks.append(_pin_np[:m].tobytes())
+    return chunks[0] if len(chunks) == 1 else b"".join(chunks)

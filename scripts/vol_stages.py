@@ -1,5 +1,5 @@
 import io, os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import modal_amd as modal
 from modal_amd.ops import gpu_available
 print("gpu:", gpu_available())

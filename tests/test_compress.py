@@ -94,6 +94,43 @@ def test_put_file_matches_put_digest(tmp_path):
         assert store.put_file(str(p)) == store.put(data)
 
 
+def test_malformed_container_raises_before_any_launch(monkeypatch):
+    """A malformed container handed to the GPU decompressor is a ValueError
+    from the host-side validator: the library is never loaded, nothing is
+    launched, and the dispatching front door neither falls back silently nor
+    returns bytes."""
+    import struct
+
+    # the container of test_snapshot_blocks_cpu.test_container_header_validation:
+    # a 1 KiB random unit repeated, whose 100-byte last segment is stored raw
+    unit = random.Random(7).randbytes(1024)
+    data = (unit * 1025)[: 1024 * 1024 + 100]
+    good = C.compress_buffer_cpu(data)
+    assert good is not None and C.decompress_buffer_cpu(good) == data
+    raw_len, comp_lens, _off = C.parse_header(good)
+    assert comp_lens[-1] == 0
+    magic, table = len(C.MAGIC), C.HEADER_FIXED
+    mutations = {
+        "truncated": good[:-1],
+        "comp_len": good[:table] + struct.pack("<I", comp_lens[0] + 1) + good[table + 4 :],
+        "raw_len": good[:magic] + struct.pack("<Q", raw_len + 1) + good[magic + 8 :],
+        "n_seg": good[: magic + 8] + struct.pack("<I", len(comp_lens) + 1) + good[table:],
+        "short": good[: table - 1],
+    }
+
+    def no_launch(*_a, **_k):
+        raise AssertionError("the ops library was loaded for a malformed container")
+
+    monkeypatch.setattr("modal_amd.ops.compress.load_lib", no_launch)
+    for name, bad in mutations.items():
+        with pytest.raises(ValueError):
+            C.decompress_buffer_gpu(bad)
+        with pytest.raises(ValueError):
+            C.decompress_buffer(bad)
+        with pytest.raises(ValueError):
+            C.parse_header(bad)
+
+
 @pytest.mark.gpu
 def test_gpu_compress_matches_cpu_decompress():
     torch = pytest.importorskip("torch")

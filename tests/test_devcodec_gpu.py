@@ -1,13 +1,15 @@
 """Device block codec (ops/devcodec.py + csrc/malz.hip) on the GPU: the plan
-kernel against numpy, encode against the existing single-buffer path byte for
-byte, decode into device memory, digest verification, and the block-addressed
-snapshot end to end. Every comparison is exact."""
+kernel against numpy, encode and both blob compress paths against a container
+assembled on the host byte for byte, decode into device memory, digest
+verification, and the block-addressed snapshot end to end. Every comparison
+is exact."""
 
 from __future__ import annotations
 
 import os
 import pickle
 import signal
+import struct
 
 import numpy as np
 import pytest
@@ -108,7 +110,7 @@ def test_plan_kernel_matches_cumsum():
     comp_d = torch.from_numpy(comp_lens).cuda()
     first_d = torch.from_numpy(first).cuda()
     raw_d = torch.from_numpy(raw_lens).cuda()
-    seg_off = torch.full((total,), -1, dtype=torch.int32, device="cuda")
+    seg_off = torch.full((total,), -1, dtype=torch.int64, device="cuda")
     payload = torch.full((len(n_segs),), -1, dtype=torch.int64, device="cuda")
     rc = lib.ma_malz_plan(
         comp_d.data_ptr(), first_d.data_ptr(), raw_d.data_ptr(), seg_off.data_ptr(),
@@ -130,30 +132,95 @@ ENCODE_CASES = {
 }
 
 
+def _host_container(lib, dev, raw: bytes):
+    """The oracle: LZ4 kernel on the device bytes ``dev`` into a strided
+    tensor, everything else (keep/raw rule, header, table, compaction) with
+    numpy and struct on the host, raw segments from the host copy ``raw``."""
+    import torch
+
+    stride, min_gain = SEG + 256, 0.95
+    n = len(raw)
+    n_seg = -(-n // SEG)
+    out = torch.empty(n_seg * stride, dtype=torch.uint8, device="cuda")
+    lens_d = torch.empty(n_seg, dtype=torch.int32, device="cuda")
+    rc = lib.ma_lz4_compress(
+        dev.data_ptr(), n, out.data_ptr(), lens_d.data_ptr(), stride, n_seg,
+        torch.cuda.current_stream().cuda_stream,
+    )
+    assert rc == 0
+    comp_lens = lens_d.cpu().numpy()
+    slots = out.cpu().numpy()
+    parts = [b"MALZ41", struct.pack("<QI", n, n_seg), comp_lens.astype("<u4").tobytes()]
+    for s, clen in enumerate(comp_lens.tolist()):
+        if clen:
+            parts.append(slots[s * stride : s * stride + clen].tobytes())
+        else:
+            parts.append(raw[s * SEG : (s + 1) * SEG])
+    if sum(len(p) for p in parts[3:]) >= n * min_gain:
+        return None
+    return b"".join(parts)
+
+
 @pytest.mark.parametrize("name", sorted(ENCODE_CASES))
 def test_encode_matches_existing_path(encoded, name):
-    from modal_amd.ops.compress import compress_buffer_gpu, decompress_buffer_cpu, parse_header
+    """The block codec, compress_buffer_gpu and compress_buffers_gpu share one
+    device encoder, so all three are held to a container assembled on the
+    host from the LZ4 kernel's raw output."""
+    from modal_amd.ops.compress import (
+        compress_buffer_gpu, compress_buffers_gpu, decompress_buffer_cpu, parse_header,
+    )
+    from modal_amd.ops.devcodec import COMPRESS_MIN
     from modal_amd.ops.hashing import content_digest
 
-    _dev, raw, blocks = encoded[name]
+    _devcodec, lib = _feature()
+    dev, raw, blocks = encoded[name]
     assert [b.compressed for b in blocks] == ENCODE_CASES[name]
     assert sum(b.raw_len for b in blocks) == len(raw)
-    off = 0
+    raw_blocks, oracles, off = [], [], 0
     for blk in blocks:
-        block = raw[off : off + blk.raw_len]
+        raw_blocks.append(raw[off : off + blk.raw_len])
+        oracles.append(_host_container(lib, dev[off : off + blk.raw_len], raw_blocks[-1]))
         off += blk.raw_len
+    batched = compress_buffers_gpu(raw_blocks)
+    for blk, block, oracle, from_batch in zip(blocks, raw_blocks, oracles, batched):
         assert blk.digest == content_digest(block)
+        assert compress_buffer_gpu(block) == oracle
+        assert from_batch == oracle
         if blk.compressed:
-            assert blk.payload == compress_buffer_gpu(block)
+            assert blk.payload == oracle
             assert decompress_buffer_cpu(blk.payload) == block
         else:
             assert blk.payload == block
+            assert oracle is None or blk.raw_len < COMPRESS_MIN
     if name == "c_mixed":
         _n, comp_lens, _off = parse_header(blocks[0].payload)
         assert any(c == 0 for c in comp_lens) and any(c != 0 for c in comp_lens)
     if name == "d_one_byte_segment":
         _n, comp_lens, _off = parse_header(blocks[0].payload)
         assert len(comp_lens) == 257
+
+
+def test_batched_compress_staged_subset():
+    """compress_buffers_gpu over a shared staging at 8 KiB-aligned offsets,
+    compressing a strict subset: picked entries equal the oracle, the others
+    are None."""
+    from modal_amd.ops.compress import compress_buffers_gpu
+    from modal_amd.ops.hashing import LEAF_SIZE
+    from modal_amd.ops.staging import stage_many_to_gpu
+
+    _devcodec, lib = _feature()
+    buffers = [
+        _pattern(MiB + 1, seed=31).tobytes(),
+        _pattern(4096, seed=32).tobytes(),
+        _pattern(2 * MiB, seed=33).tobytes(),
+    ]
+    src, offsets = stage_many_to_gpu(buffers, align=LEAF_SIZE)
+    assert offsets == [0, MiB + LEAF_SIZE, MiB + 2 * LEAF_SIZE]
+    got = compress_buffers_gpu(buffers, staged=(src, offsets), only=[0, 2])
+    assert got[1] is None
+    for i in (0, 2):
+        oracle = _host_container(lib, src[offsets[i] : offsets[i] + len(buffers[i])], buffers[i])
+        assert oracle is not None and got[i] == oracle
 
 
 @pytest.mark.parametrize("name", sorted(ENCODE_CASES))

@@ -36,6 +36,31 @@ def test_batch_matches_single_cpu():
     assert content_digests_batch(buffers) == [content_digest(b) for b in buffers]
 
 
+def test_leaf_table_matches_per_leaf_loop():
+    from modal_amd.ops.hashing import leaf_table
+
+    MiB = 1024 * 1024
+    lengths = [1, LEAF_SIZE - 1, LEAF_SIZE, LEAF_SIZE + 1, 8 * MiB, 8 * MiB + 12345]
+    packed, pos = [], 0
+    for n in lengths:  # back to back at leaf-aligned offsets, as staged
+        packed.append((pos, n))
+        pos += -(-n // LEAF_SIZE) * LEAF_SIZE
+    shifted = [(3 * LEAF_SIZE + 7 + base, n) for base, n in reversed(packed)]
+    for spans in ([(0, n) for n in lengths], packed, shifted, [(5, 1)]):
+        want_off, want_len, want_counts = [], [], []
+        for base, n in spans:
+            leaves = range(0, n, LEAF_SIZE)
+            want_off += [base + o for o in leaves]
+            want_len += [min(LEAF_SIZE, n - o) for o in leaves]
+            want_counts.append(len(leaves))
+        offsets, lens, counts = leaf_table(spans)
+        assert offsets.dtype == lens.dtype == "int64"
+        assert offsets.tolist() == want_off
+        assert lens.tolist() == want_len
+        assert list(counts) == want_counts
+        assert sum(want_len) == sum(n for _b, n in spans)
+
+
 def test_blobstore_put_many(tmp_path):
     from modal_amd.scheduler.blobs import BlobStore
 
