@@ -405,7 +405,7 @@ py::bytes malz_decompress(py::bytes blob) {
   py::bytes out_obj(nullptr, (ssize_t)raw_len);
   uint8_t* out = (uint8_t*)PyBytes_AsString(out_obj.ptr());
   const uint8_t* src = (const uint8_t*)buf;
-  bool ok = true;
+  std::atomic<bool> ok{true};  // written from every worker thread
   {
     py::gil_scoped_release release;
     parallel_for(n_seg, [&](size_t lo, size_t hi) {
@@ -416,12 +416,12 @@ py::bytes malz_decompress(py::bytes blob) {
           std::memcpy(out + seg_off, src + seg_payload_off[i], seg_len);
         } else if (!lz4_decompress_one(src + seg_payload_off[i], comp_lens[i],
                                        out + seg_off, seg_len)) {
-          ok = false;
+          ok.store(false, std::memory_order_relaxed);
         }
       }
     });
   }
-  if (!ok) throw std::runtime_error("corrupt LZ4 segment");
+  if (!ok.load()) throw std::runtime_error("corrupt LZ4 segment");
   return out_obj;
 }
 

@@ -35,6 +35,7 @@ HEADER_FIXED = len(MAGIC) + 12  # magic + u64 raw_len + u32 n_seg
 SEG_SIZE = 4096
 OUT_STRIDE = SEG_SIZE + 256
 MIN_GAIN = 0.95  # store raw unless compression saves >=5%
+_STATUS_CLEAN = 2**31 - 1  # decompress status word when no segment is corrupt
 
 
 def _header(raw_len: int, comp_lens: Sequence[int]) -> bytes:
@@ -146,10 +147,15 @@ def compress_buffer_cpu(data: bytes) -> Optional[bytes]:
 
 
 def decompress_buffer_cpu(blob: bytes) -> bytes:
+    """Raw bytes of a container; ``ValueError`` on a malformed header or a
+    corrupt LZ4 segment, whichever backend decodes."""
     raw_len, comp_lens, off = validate_container(blob)
     core = _native_core()
     if core is not None:
-        return core.malz_decompress(bytes(blob))
+        try:
+            return core.malz_decompress(bytes(blob))
+        except RuntimeError as exc:  # the core's std::runtime_error
+            raise ValueError(f"LZ4 container corrupt: {exc}") from None
     from ..utils import lz4ref
 
     out = bytearray()
@@ -160,7 +166,10 @@ def decompress_buffer_cpu(blob: bytes) -> bytes:
             out += blob[pos : pos + seg_raw]
             pos += seg_raw
         else:
-            out += lz4ref.decompress_block(blob[pos : pos + clen], seg_raw)
+            try:
+                out += lz4ref.decompress_block(blob[pos : pos + clen], seg_raw)
+            except ValueError as exc:
+                raise ValueError(f"{corrupt_message(i + 1)}: {exc}") from None
             pos += clen
     return bytes(out)
 
@@ -333,7 +342,9 @@ def decompress_run_gpu(
     comp_offs -= eff  # exclusive
     offs_d = _to_dev(comp_offs)
     lens_d = _to_dev(comp_lens)
-    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    # the kernel takes the min of 1 + index over the corrupt segments, so the
+    # answer does not depend on which lane stores last; the max means none
+    status = torch.full((1,), _STATUS_CLEAN, dtype=torch.int32, device="cuda")
     _check(
         lib.ma_lz4_decompress(
             comp, offs_d.data_ptr(), lens_d.data_ptr(), dst,
@@ -342,7 +353,8 @@ def decompress_run_gpu(
         ),
         "lz4 decompress kernel",
     )
-    return int(status.item())  # syncs: the tables may be freed
+    first_bad = int(status.item())  # syncs: the tables may be freed
+    return 0 if first_bad == _STATUS_CLEAN else first_bad
 
 
 def corrupt_message(status: int) -> str:

@@ -194,6 +194,8 @@ __device__ int lz4_decompress_segment(const uint8_t* __restrict__ src, int src_l
   return op;
 }
 
+// *status comes in as INT32_MAX and leaves as the min of seg + 1 over the
+// segments that did not decode to their exact raw length (untouched: none).
 extern "C" __global__ __launch_bounds__(256) void lz4_decompress_kernel(
     const uint8_t* __restrict__ comp,       // compacted segment data
     const int64_t* __restrict__ comp_offs,  // per-segment offset into comp
@@ -213,7 +215,7 @@ extern "C" __global__ __launch_bounds__(256) void lz4_decompress_kernel(
   } else {
     written = lz4_decompress_segment(sp, clen, dst + start, raw_len);
   }
-  if (written != raw_len) atomicExch(status, seg + 1);
+  if (written != raw_len) atomicMin(status, seg + 1);  // the FIRST corrupt one
 }
 
 extern "C" int ma_lz4_compress(const void* src, long src_len, void* dst,
