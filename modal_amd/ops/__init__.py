@@ -70,6 +70,19 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_int,
                 ctypes.c_void_p,
             ]
+            ptr, i32 = ctypes.c_void_p, ctypes.c_int
+            lib.ma_fpz_rank.restype = ctypes.c_int
+            lib.ma_fpz_rank.argtypes = [ptr] * 3 + [i32] + [ptr] * 3 + [i32, ptr]
+            lib.ma_fpz_encode.restype = ctypes.c_int
+            lib.ma_fpz_encode.argtypes = (
+                [ptr] * 5 + [i32, ptr, i32, ptr, i32, ctypes.c_long, ptr]
+            )
+            lib.ma_fpz_assemble.restype = ctypes.c_int
+            lib.ma_fpz_assemble.argtypes = (
+                [ptr] * 3 + [i32] + [ptr] * 5 + [i32] + [ptr] * 2 + [i32, ptr]
+            )
+            lib.ma_fpz_decode.restype = ctypes.c_int
+            lib.ma_fpz_decode.argtypes = [ptr] * 10 + [i32, ptr]
             from .rawmem import _bind as _bind_rawmem
 
             _bind_rawmem(lib)

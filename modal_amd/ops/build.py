@@ -12,7 +12,8 @@ import sys
 
 _THIS_DIR = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_THIS_DIR, "csrc")
-SOURCES = ["sha256.hip", "pack.hip", "lz4.hip", "rawmem.hip", "malz.hip"]
+SOURCES = ["sha256.hip", "pack.hip", "lz4.hip", "rawmem.hip", "malz.hip", "fpz.hip"]
+HEADERS = ["malz_common.h"]  # included by SOURCES: a change rebuilds
 
 
 def _hipcc() -> str:
@@ -29,7 +30,7 @@ def needs_build() -> bool:
     if not os.path.exists(out):
         return True
     out_mtime = os.path.getmtime(out)
-    for src in SOURCES:
+    for src in SOURCES + HEADERS:
         if os.path.getmtime(os.path.join(_CSRC, src)) > out_mtime:
             return True
     return False

@@ -107,6 +107,13 @@ def is_compressed(blob: bytes) -> bool:
     return blob.startswith(MAGIC)
 
 
+def _is_float_plane(blob: bytes) -> bool:
+    """A stored container is one of ours, MALZ41 or MAFP10 (ops/fpcodec.py):
+    whether a blob is compressed at all is out of band (the ``.z`` suffix),
+    so the magic only has to tell the two apart."""
+    return bytes(blob[:6]) == b"MAFP10"
+
+
 # ---------------------------------------------------------------------------
 # CPU reference paths
 # ---------------------------------------------------------------------------
@@ -149,6 +156,10 @@ def compress_buffer_cpu(data: bytes) -> Optional[bytes]:
 def decompress_buffer_cpu(blob: bytes) -> bytes:
     """Raw bytes of a container; ``ValueError`` on a malformed header or a
     corrupt LZ4 segment, whichever backend decodes."""
+    if _is_float_plane(blob):
+        from . import fpcodec
+
+        return fpcodec.decompress_buffer_cpu(blob)
     raw_len, comp_lens, off = validate_container(blob)
     core = _native_core()
     if core is not None:
@@ -362,6 +373,10 @@ def corrupt_message(status: int) -> str:
 
 
 def decompress_buffer_gpu(blob: bytes) -> bytes:
+    if _is_float_plane(blob):
+        from . import fpcodec
+
+        return fpcodec.decompress_buffer_gpu(blob)
     raw_len, comp_lens, off = validate_container(blob)  # before any launch
     lib = load_lib(required=True)
     import torch

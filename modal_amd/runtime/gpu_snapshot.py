@@ -309,14 +309,24 @@ def restore_payload(data: bytes, store: Any = None) -> dict:
 _RESTORE_CHUNK_BLOCKS = 8
 
 
-def capture_manifest(store: Any) -> bytes:
+def capture_manifest(store: Any, float_codec: bool = False) -> bytes:
     """Block-addressed snapshot: every registered tensor and tracked raw
     allocation is cut into CAS blocks, hashed and compressed where it lives
     (CUDA memory on the GPU through ops/devcodec.py, CPU tensors on the
     host), each new block goes to ``store`` and only the digests are
     returned. Blocks the store already has are neither compressed nor
-    copied, so a second snapshot of unchanged state costs its hashing."""
+    copied, so a second snapshot of unchanged state costs its hashing.
+
+    ``float_codec`` offers the blocks of registered bf16/fp16/fp32 tensors
+    that LZ4 declined to the float-plane codec (ops/fpcodec.py). Raw
+    allocations carry no element type and are never offered. Digests are of
+    the raw blocks, so the manifest is the same either way, and restore
+    needs no flag: a stored container names its codec."""
     from ..ops import devcodec, rawmem
+
+    def hint(t: Any) -> int:
+        fits = float_codec and t.dtype.is_floating_point and t.element_size() in (2, 4)
+        return t.element_size() if fits else 0
 
     def entry_for(nbytes: int, **extra: Any) -> dict:
         return {"blocks": [], "block_lens": [], "nbytes": nbytes, **extra}
@@ -329,7 +339,8 @@ def capture_manifest(store: Any) -> bytes:
 
     tensors: dict[str, dict] = {}
     raw: dict[str, dict] = {}
-    on_device: list[tuple[dict, int, int, Any]] = []  # (entry, ptr, nbytes, keepalive)
+    # (entry, ptr, nbytes, element size hint, keepalive)
+    on_device: list[tuple[dict, int, int, int, Any]] = []
     if _registered_tensors:
         import torch
 
@@ -345,10 +356,11 @@ def capture_manifest(store: Any) -> bytes:
                 continue
             src = t.detach().contiguous()
             if src.is_cuda:
-                on_device.append((entry, src.data_ptr(), nbytes, src))
+                on_device.append((entry, src.data_ptr(), nbytes, hint(t), src))
             else:
                 # byte-level view: numpy() would reject bf16/fp8 dtypes
-                for blk in devcodec.encode_host(src.reshape(-1).view(torch.uint8).numpy()):
+                flat = src.reshape(-1).view(torch.uint8).numpy()
+                for blk in devcodec.encode_host(flat, elem_size=hint(t)):
                     add(entry, blk)
     lib = rawmem.load_lib()
     if lib is not None:
@@ -358,10 +370,11 @@ def capture_manifest(store: Any) -> bytes:
                 continue  # released (paged out) rows have no device memory
             entry = raw[key] = entry_for(found[1])
             if found[1]:
-                on_device.append((entry, found[0], found[1], None))
+                on_device.append((entry, found[0], found[1], 0, None))
     if on_device:
-        objects = [(ptr, nbytes) for _e, ptr, nbytes, _k in on_device]
-        for oi, blk in devcodec.iter_encode_device(objects, known=store.has):
+        objects = [(ptr, nbytes) for _e, ptr, nbytes, _es, _k in on_device]
+        hints = [es for _e, _ptr, _n, es, _k in on_device]
+        for oi, blk in devcodec.iter_encode_device(objects, known=store.has, elem_sizes=hints):
             add(on_device[oi][0], blk)
     payload = {
         "version": 2,

@@ -195,14 +195,15 @@ class WorkerRPCTarget:
 
         return await asyncio.get_running_loop().run_in_executor(None, capture_payload)
 
-    async def snapshot_manifest(self) -> bytes:
+    async def snapshot_manifest(self, float_codec: bool = False) -> bytes:
         """Block-addressed snapshot (gpu_snapshot.capture_manifest): the
         state's blocks go straight into the shared CAS, encoded on the GPU
-        where they live; only the small manifest crosses the socket."""
+        where they live; only the small manifest crosses the socket.
+        ``float_codec`` offers float tensors to the float-plane codec."""
         from .gpu_snapshot import capture_manifest
 
         return await asyncio.get_running_loop().run_in_executor(
-            None, capture_manifest, self._runtime.blob_store
+            None, capture_manifest, self._runtime.blob_store, float_codec
         )
 
 

@@ -1387,7 +1387,9 @@ class Scheduler:
         }
 
     # -- worker GPU snapshots ---------------------------------------------
-    async def worker_snapshot(self, worker_id: int, block_addressed: bool = False) -> dict:
+    async def worker_snapshot(
+        self, worker_id: int, block_addressed: bool = False, float_codec: bool = False
+    ) -> dict:
         """Capture a worker's snapshot-visible GPU state (registered
         tensors + tracked raw hipMalloc allocations + RNG) into the CAS.
         Parity: the snapshot half of ContainerCheckpoint
@@ -1395,12 +1397,18 @@ class Scheduler:
 
         block_addressed=True: the worker encodes its state into CAS blocks
         itself (on the GPU for device memory) and returns only a manifest
-        of digests; unchanged blocks of a later snapshot are stored once."""
+        of digests; unchanged blocks of a later snapshot are stored once.
+
+        float_codec=True (needs block_addressed): blocks of float tensors
+        that LZ4 declined are stored as MAFP10 containers (ops/fpcodec.py)."""
+        if float_codec and not block_addressed:
+            raise InvalidError("float_codec needs block_addressed=True")
         w = self.pool.workers.get(int(worker_id))
         if w is None:
             raise NotFoundError(f"worker {worker_id} not connected")
         rpc = "snapshot_manifest" if block_addressed else "snapshot_state"
-        data = await w.conn.call(rpc, timeout=300)
+        params = {"float_codec": True} if float_codec else None
+        data = await w.conn.call(rpc, params, timeout=300)
         blob_id = self.blob_store.put(data)
         return {"snapshot_id": blob_id}
 

@@ -4,8 +4,9 @@ v2 (block-addressed manifest, encoded on the device) on one GPU, one process.
 For a CUDA tensor of --size-mib per kind -- "pattern" (one 1 KiB unit
 repeated: compressible, and every 8 MiB block identical, so the capture
 dedups against itself), "distinct" (a different 1 KiB unit per block:
-compressible, no dedup) and "random" (incompressible) -- capture + restore
-through both paths, N timed
+compressible, no dedup), "random" (incompressible) and, when named, "bf16"
+(N(0,1) weights as bfloat16: LZ4 stores them raw, --float-codec offers them
+to the float-plane codec) -- capture + restore through both paths, N timed
 runs after one warm-up, median and min-max of host wall time around work
 that ends in torch.cuda.synchronize(). v2 also reports the bytes the CAS
 stored, the time of a second capture (every block already present), and the
@@ -13,6 +14,7 @@ longest single tail-hash dispatch (one lane per short block), measured on a
 tensor of --tail-bytes.
 
     python scripts/prof_snapshot.py --size-mib 1024 --runs 5
+    python scripts/prof_snapshot.py --kinds bf16 --float-codec
 """
 
 from __future__ import annotations
@@ -38,6 +40,8 @@ MiB = 1024 * 1024
 
 def make_tensor(kind: str, nbytes: int) -> torch.Tensor:
     gen = torch.Generator(device="cuda").manual_seed(1234)
+    if kind == "bf16":
+        return torch.randn(nbytes // 2, device="cuda", generator=gen).to(torch.bfloat16)
     if kind == "random":
         return torch.randint(0, 256, (nbytes,), dtype=torch.uint8, device="cuda", generator=gen)
     if kind == "distinct":
@@ -83,7 +87,7 @@ def check(t: torch.Tensor) -> None:
     assert got.is_cuda and torch.equal(got, t), "restore changed the bytes"
 
 
-def run_kind(kind: str, nbytes: int, runs: int) -> dict:
+def run_kind(kind: str, nbytes: int, runs: int, float_codec: bool = False) -> dict:
     t = make_tensor(kind, nbytes)
     times: dict[str, list] = {k: [] for k in ("v1_capture", "v1_restore", "v2_capture", "v2_restore", "v2_second_capture")}
     stored = 0
@@ -100,9 +104,9 @@ def run_kind(kind: str, nbytes: int, runs: int) -> dict:
         try:
             store = BlobStore(root)
             reset(t)
-            c2, manifest = timed(lambda: gs.capture_manifest(store))
+            c2, manifest = timed(lambda: gs.capture_manifest(store, float_codec=float_codec))
             stored = stored_bytes(root)
-            c2b, _ = timed(lambda: gs.capture_manifest(store))
+            c2b, _ = timed(lambda: gs.capture_manifest(store, float_codec=float_codec))
             assert stored_bytes(root) == stored
             gs._registered_tensors.clear()
             r2, _ = timed(lambda: gs.restore_payload(manifest, store))
@@ -112,7 +116,7 @@ def run_kind(kind: str, nbytes: int, runs: int) -> dict:
         if it:
             for key, val in zip(times, (c1, r1, c2, r2, c2b)):
                 times[key].append(val)
-    out = {"kind": kind, "nbytes": nbytes, "v1_payload_bytes": v1_bytes, "v2_stored_bytes": stored}
+    out = {"kind": kind, "float_codec": float_codec, "nbytes": nbytes, "v1_payload_bytes": v1_bytes, "v2_stored_bytes": stored}
     out.update({key: summary(vals) for key, vals in times.items()})
     return out
 
@@ -131,9 +135,11 @@ def main() -> None:
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--tail-bytes", type=int, default=8 * MiB - 1)
     ap.add_argument("--kinds", default="pattern,distinct,random")
+    ap.add_argument("--float-codec", action="store_true",
+                    help="capture_manifest(float_codec=True): MAFP10 for float tensors")
     args = ap.parse_args()
     for kind in args.kinds.split(","):
-        print(json.dumps(run_kind(kind, args.size_mib * MiB, args.runs)), flush=True)
+        print(json.dumps(run_kind(kind, args.size_mib * MiB, args.runs, args.float_codec)), flush=True)
     print(json.dumps(tail_hash(args.tail_bytes)), flush=True)
 
 
