@@ -73,6 +73,10 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
             ptr, i32 = ctypes.c_void_p, ctypes.c_int
             lib.ma_fpz_rank.restype = ctypes.c_int
             lib.ma_fpz_rank.argtypes = [ptr] * 3 + [i32] + [ptr] * 3 + [i32, ptr]
+            lib.ma_fpz_probe.restype = ctypes.c_int
+            lib.ma_fpz_probe.argtypes = [ptr] * 4 + [i32, ptr]
+            lib.ma_fpz_rank_counts.restype = ctypes.c_int
+            lib.ma_fpz_rank_counts.argtypes = [ptr] * 3 + [i32, ptr]
             lib.ma_fpz_encode.restype = ctypes.c_int
             lib.ma_fpz_encode.argtypes = (
                 [ptr] * 5 + [i32, ptr, i32, ptr, i32, ctypes.c_long, ptr]

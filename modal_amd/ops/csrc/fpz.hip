@@ -5,6 +5,8 @@
 // element as its rank in a per-block frequency order, at a bit width chosen
 // per 4 KiB segment, and leaves the low bytes alone.
 //
+//   probe     per block: the histograms at es 2 AND 4 in one pass over the
+//             bytes, for callers that have to find the element size
 //   hist      per block: LDS histogram of the top bytes, one global merge
 //   rank      per block: 256 threads each find their byte's rank by counting
 //   encode    one wavefront per segment -> its stride slot + comp_lens, the
@@ -113,6 +115,123 @@ extern "C" __global__ __launch_bounds__(256) void fpz_rank_kernel(
   }
   order[b * 256 + r] = (uint8_t)tid;
   rank_of[b * 256 + tid] = (uint8_t)r;
+}
+
+// ---------------------------------------------------------------------------
+// probe: both histograms of a block in one pass
+// ---------------------------------------------------------------------------
+//
+// counts[b][0] is what fpz_hist_kernel gives at es = 2 (the byte at 2k+1 of
+// every whole 2-byte element), counts[b][1] what it gives at es = 4 (the byte
+// at 4k+3). A byte at span offset i is a top byte at es = 2 when i is odd and
+// at es = 4 when i % 4 == 3, and "i < raw_len" is then the same as "the
+// element is whole". So the kernel keeps two LDS histograms, one of the
+// bytes at i % 4 == 1 and one of the bytes at i % 4 == 3, and the merge adds
+// the second into both tables.
+//
+// Loads. A lane reads aligned 16-byte chunks, starting at the chunk the
+// span's first byte lives in, so every chunk loaded holds a byte of the span
+// and every source byte is read once at any source alignment. Within an
+// aligned dword the two bytes wanted sit at (1 + mis) % 4 and (3 + mis) % 4,
+// mis the span's misalignment: two shifts that are the same for the whole
+// block. Only the first and the last chunk of a span can hold bytes outside
+// it; those two take the path that checks 0 <= i < raw_len per byte.
+//
+// LDS layout. Gaussian floats put most elements on a few bins (two bins hold
+// 57 % of N(0,1) bf16). fpz_hist_kernel's bins[copy][256] puts every copy of
+// a bin on one bank (bank = bin % 32), so lanes of one wavefront that meet on
+// a popular bin serialise whether or not they use different copies. Here the
+// copy is the minor index, bins[bin][copy] with copy = lane % PROBE_COPIES,
+// so the bank depends on the lane and hardly on the data. At 32 copies the
+// bank is lane % 32 and the 32 lanes of an LDS lane group never meet, for
+// 2 x 256 x 32 x 4 B = 64 KiB (two workgroups per CU). At 16 copies (32 KiB)
+// lanes l and l + 16 of a group share a bank when their bins have the same
+// parity, a two-way conflict at worst. The merge reads a bin's copies rotated
+// by the thread index to stay off one bank.
+//
+// Measured on an MI355X (hipEvent times, median of 10 interleaved launches,
+// 64 MiB of N(0,1) bf16, spans at 0 or 2 mod 16), fpz_hist_kernel at es = 2
+// on the same bytes beside it:
+//                     8 x 8 MiB spans   64 x 1 MiB spans
+//   hist (es = 2)     67.8 us           44.6 us
+//   probe, 32 copies  18.0 us           32.2 us
+//   probe, 16 copies  17.8 us           20.6 us
+// With 8 MiB spans the two layouts tie: the loads, not the LDS, set the time.
+// With 1 MiB spans a workgroup has 16 KiB of source, and zeroing and merging
+// 64 KiB of bins shows. So 16 copies. More in profiles/README.md,
+// "Element-size probe".
+
+#ifndef PROBE_COPIES
+#define PROBE_COPIES 16
+#endif
+#define PROBE_BLOCK 256
+#define PROBE_GROUPS 64
+
+#define PROBE_UNROLL 4  // 16-byte loads a lane has in flight
+
+// The two top-byte candidates of each dword of chunk q of a span of n bytes.
+__device__ __forceinline__ void probe_count(const uint4 v, int64_t q, int mis16, int64_t n,
+                                            uint32_t* mine1, uint32_t* mine3) {
+  const int j1 = (1 + mis16) & 3, j3 = (3 + mis16) & 3;  // byte of a dword at i % 4 == 1, 3
+  const int sh1 = 8 * j1, sh3 = 8 * j3;
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  const int64_t i0 = 16 * q - mis16;  // span offset of the chunk's first byte
+  if (i0 >= 0 && i0 + 16 <= n) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      atomicAdd(mine1 + ((w[d] >> sh1) & 255u) * PROBE_COPIES, 1u);
+      atomicAdd(mine3 + ((w[d] >> sh3) & 255u) * PROBE_COPIES, 1u);
+    }
+  } else {  // the span's first or last chunk: count only its own bytes
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const int64_t i1 = i0 + 4 * d + j1, i3 = i0 + 4 * d + j3;
+      if (i1 >= 0 && i1 < n) atomicAdd(mine1 + ((w[d] >> sh1) & 255u) * PROBE_COPIES, 1u);
+      if (i3 >= 0 && i3 < n) atomicAdd(mine3 + ((w[d] >> sh3) & 255u) * PROBE_COPIES, 1u);
+    }
+  }
+}
+
+extern "C" __global__ __launch_bounds__(PROBE_BLOCK) void fpz_probe_kernel(
+    const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_src_off,
+    const int64_t* __restrict__ blk_raw_len, uint32_t* __restrict__ counts, int blk_base) {
+  __shared__ uint32_t bins[2][256 * PROBE_COPIES];
+  const int b = blk_base + blockIdx.y;
+  const int tid = threadIdx.x;
+  const int64_t n = blk_raw_len[b];
+  if (n <= 0) return;
+  const uint8_t* first = src + blk_src_off[b];
+  const int mis16 = (int)(reinterpret_cast<uintptr_t>(first) & 15);
+  const int64_t n_chunks = (mis16 + n + 15) >> 4;  // the last one holds byte n - 1
+  if ((int64_t)blockIdx.x * PROBE_BLOCK >= n_chunks) return;  // nothing here: no merge either
+
+  uint4* z = reinterpret_cast<uint4*>(&bins[0][0]);
+  for (int k = tid; k < 2 * 256 * PROBE_COPIES / 4; k += PROBE_BLOCK) z[k] = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+
+  const uint4* chunks = reinterpret_cast<const uint4*>(first - mis16);
+  uint32_t* mine1 = &bins[0][tid & (PROBE_COPIES - 1)];
+  uint32_t* mine3 = &bins[1][tid & (PROBE_COPIES - 1)];
+  const int64_t step = (int64_t)gridDim.x * PROBE_BLOCK;
+  int64_t q = (int64_t)blockIdx.x * PROBE_BLOCK + tid;
+  for (; q + (PROBE_UNROLL - 1) * step < n_chunks; q += PROBE_UNROLL * step) {
+    uint4 v[PROBE_UNROLL];
+#pragma unroll
+    for (int u = 0; u < PROBE_UNROLL; ++u) v[u] = chunks[q + u * step];
+#pragma unroll
+    for (int u = 0; u < PROBE_UNROLL; ++u) probe_count(v[u], q + u * step, mis16, n, mine1, mine3);
+  }
+  for (; q < n_chunks; q += step) probe_count(chunks[q], q, mis16, n, mine1, mine3);
+  __syncthreads();
+  uint32_t t1 = 0, t3 = 0;
+  for (int k = 0; k < PROBE_COPIES; ++k) {
+    const int c = (k + tid) & (PROBE_COPIES - 1);
+    t1 += bins[0][tid * PROBE_COPIES + c];
+    t3 += bins[1][tid * PROBE_COPIES + c];
+  }
+  uint32_t* out = counts + (int64_t)b * 512;
+  if (t1 + t3) atomicAdd(&out[tid], t1 + t3);
+  if (t3) atomicAdd(&out[256 + tid], t3);
 }
 
 // ---------------------------------------------------------------------------
@@ -400,6 +519,32 @@ extern "C" int ma_fpz_rank(const void* src, const void* blk_src_off, const void*
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return (int)err;
   }
+  hipLaunchKernelGGL(fpz_rank_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream,
+                     (const uint32_t*)counts, (uint8_t*)order, (uint8_t*)rank_of);
+  return (int)hipGetLastError();
+}
+
+// counts (n_blocks x 2 x 256 u32) must come in zeroed: [b][0] the es = 2
+// histogram of block b, [b][1] the es = 4 one.
+extern "C" int ma_fpz_probe(const void* src, const void* blk_src_off, const void* blk_raw_len,
+                            void* counts, int n_blocks, void* stream) {
+  for (int base = 0; base < n_blocks; base += MAX_GRID_Y) {
+    int ny = n_blocks - base < MAX_GRID_Y ? n_blocks - base : MAX_GRID_Y;
+    hipLaunchKernelGGL(fpz_probe_kernel, dim3(PROBE_GROUPS, ny), dim3(PROBE_BLOCK), 0,
+                       (hipStream_t)stream, (const uint8_t*)src,
+                       (const int64_t*)blk_src_off, (const int64_t*)blk_raw_len,
+                       (uint32_t*)counts, base);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return (int)err;
+  }
+  return 0;
+}
+
+// The rank tables of histograms the caller already has (n_blocks x 256 u32,
+// a probe's for instance): ma_fpz_rank without its histogram pass.
+extern "C" int ma_fpz_rank_counts(const void* counts, void* order, void* rank_of, int n_blocks,
+                                  void* stream) {
+  if (n_blocks <= 0) return 0;
   hipLaunchKernelGGL(fpz_rank_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream,
                      (const uint32_t*)counts, (uint8_t*)order, (uint8_t*)rank_of);
   return (int)hipGetLastError();

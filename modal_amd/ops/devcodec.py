@@ -12,8 +12,10 @@ compressed bytes H2D and decompresses straight into the destination
 allocation through ``compress.decompress_run_gpu``.
 
 An object the caller hints as float data (``elem_size`` 2 or 4) offers the
-blocks LZ4 declined to the float-plane codec (ops/fpcodec.py, MAFP10); a
-stored container's magic selects its validator and decoder.
+blocks LZ4 declined to the float-plane codec (ops/fpcodec.py, MAFP10); an
+object of no known element type (``fpcodec.AUTO``) has those blocks probed on
+the device for the element size at which the codec pays, if any. A stored
+container's magic selects its validator and decoder.
 
 What this module adds to those is the block layer: digests, skipping blocks
 the CAS already has, the cached 64 MiB scratch with its out-of-memory
@@ -42,6 +44,7 @@ from .staging import copy_from_device, copy_to_device
 WINDOW = 64 * 1024 * 1024  # source bytes encoded per plan/assemble round
 COMPRESS_MIN = BlobStore.COMPRESS_MIN
 RUN_MAX_BLOCKS = 128  # decode: blocks per decompress launch, at most
+_ELEM_SIZES = (0, *fpcodec.ELEM_SIZES, fpcodec.AUTO)  # what an element size hint may be
 _TREE_GROUP = 8  # verify: full blocks whose leaves share one hash dispatch
 
 
@@ -167,7 +170,9 @@ def _encode_window(
     ``digests`` holds the short blocks' digests; full blocks are None. With
     ``elem_size`` 2 or 4 the blocks LZ4 declined go through the float-plane
     codec on the same scratch (LZ4 first: a zero-filled float tensor is 0.4 %
-    under LZ4 and 56 % under MAFP10)."""
+    under LZ4 and 56 % under MAFP10). With ``fpcodec.AUTO`` they are probed
+    first and each goes through it at the element size the probe found, or
+    stays raw where it found none."""
     tree = [i for i, d in enumerate(digests) if d is None]
     for i, d in zip(tree, _tree_digests(lib, ptr, [spans[i] for i in tree])):
         digests[i] = d
@@ -176,8 +181,22 @@ def _encode_window(
     containers = dict(
         zip(cand, compress.compress_spans_gpu(lib, ptr, [spans[i] for i in cand], sc))
     )
-    if elem_size:
-        left = [i for i in cand if containers[i] is None]
+    left = [i for i in cand if containers[i] is None] if elem_size else []
+    if elem_size == fpcodec.AUTO and left:
+        # one probe of all of them, then one encode per element size it
+        # found, each on its rows of the probe's tables
+        found, tables = fpcodec.probe_spans_gpu(lib, ptr, [spans[i] for i in left])
+        for col, es in enumerate(fpcodec.ELEM_SIZES):
+            rows = [k for k, e in enumerate(found) if e == es]
+            if rows:
+                # the usual window is of one kind: no index tensor to upload
+                mine = tables if len(rows) == len(found) else tables[rows]
+                z = fpcodec.compress_spans_gpu(
+                    lib, ptr, [spans[left[k]] for k in rows], es, sc,
+                    counts=mine[:, col].contiguous(),
+                )
+                containers.update(zip([left[k] for k in rows], z))
+    elif left:
         containers.update(
             zip(left, fpcodec.compress_spans_gpu(lib, ptr, [spans[i] for i in left], elem_size, sc))
         )
@@ -206,12 +225,14 @@ def iter_encode_device(
     caller already has the block: it is yielded with ``payload=None`` and is
     neither compressed nor copied. ``elem_sizes`` has one entry per object:
     2 or 4 offers the blocks LZ4 declined to the float-plane codec
-    (ops/fpcodec.py), 0 does not; digests are of the RAW block either way."""
+    (ops/fpcodec.py), ``fpcodec.AUTO`` offers them at the element size a
+    probe of their bytes finds (per block; none: raw), 0 does not; digests
+    are of the RAW block either way."""
     _check_block_size(block_size)
     if elem_sizes is None:
         elem_sizes = [0] * len(objects)
-    if len(elem_sizes) != len(objects) or any(es not in (0, 2, 4) for es in elem_sizes):
-        raise ValueError("elem_sizes needs one of 0, 2, 4 per object")
+    if len(elem_sizes) != len(objects) or any(es not in _ELEM_SIZES for es in elem_sizes):
+        raise ValueError("elem_sizes needs one of 0, 2, 4, fpcodec.AUTO per object")
     lib = load_lib(required=True)
     all_spans = [_spans(nbytes, block_size) for _ptr, nbytes in objects]
     with _codec_lock:
@@ -259,7 +280,8 @@ def _tensor_span(t: Any) -> tuple[int, int]:
 def encode_tensor(
     t: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0
 ) -> list[EncodedBlock]:
-    """``elem_size`` is the caller's to give: it is not inferred from t."""
+    """``elem_size`` is the caller's to give: it is not inferred from t's
+    dtype (``fpcodec.AUTO`` infers it from the bytes)."""
     ptr, nbytes = _tensor_span(t)
     return encode_device(ptr, nbytes, block_size=block_size, elem_size=elem_size)
 
@@ -356,10 +378,11 @@ def decode_tensor(blocks: Sequence, t: Any, *, verify: bool = True) -> None:
 def encode_host(
     data: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0
 ) -> list[EncodedBlock]:
-    """Same manifest from host bytes (CPU tensors, CPU-only processes)."""
+    """Same manifest from host bytes (CPU tensors, CPU-only processes).
+    ``fpcodec.AUTO`` runs the probe's numpy twin on every block LZ4 declined."""
     _check_block_size(block_size)
-    if elem_size not in (0, 2, 4):
-        raise ValueError("elem_size is one of 0, 2, 4")
+    if elem_size not in _ELEM_SIZES:
+        raise ValueError("elem_size is one of 0, 2, 4, fpcodec.AUTO")
     from .compress import compress_buffer
 
     view = memoryview(data).cast("B")
@@ -367,8 +390,11 @@ def encode_host(
     for off, ln in _spans(len(view), block_size):
         block = bytes(view[off : off + ln])
         z = compress_buffer(block) if ln >= COMPRESS_MIN else None
-        if z is None and elem_size and ln >= COMPRESS_MIN:
-            z = fpcodec.compress_buffer(block, elem_size)
+        es = elem_size
+        if z is None and es == fpcodec.AUTO and ln >= COMPRESS_MIN:
+            es = fpcodec.choose_elem_size(*fpcodec.probe_counts_cpu(block), ln)[0]
+        if z is None and es and ln >= COMPRESS_MIN:
+            z = fpcodec.compress_buffer(block, es)
         if z is not None:
             blocks.append(EncodedBlock(content_digest(block), ln, z, True))
         else:

@@ -31,6 +31,11 @@ on ties; the segment is coded only if L % es == 0 and hi < m, so
 seg_len = m*(es-1) + hi < L. The container is kept under the one 5 % rule,
 ``compress.worth_keeping``.
 
+A caller that does not know ``es`` (untyped device memory) asks the bytes:
+the probe gives the block's top-byte histograms at both element sizes and
+``choose_elem_size`` picks the one at which the container comes out smaller,
+or none.
+
 Everything that touches the format lives here once: the validator, the
 numpy codec (the model the kernels in csrc/fpz.hip are held to byte for
 byte, and the reader of GPU-less processes), the device encoder and the
@@ -220,6 +225,77 @@ def compress_buffer_cpu(data: Any, es: int) -> Optional[bytes]:
     return _header(n, es, order, seg_lens) + payload.tobytes()
 
 
+# ---------------------------------------------------------------------------
+# the element-size probe: its numpy twin and the rule
+# ---------------------------------------------------------------------------
+
+#: "find the element size in the bytes": what callers that have no element
+#: type pass where 0, 2 or 4 goes
+AUTO = -1
+
+
+def probe_counts_cpu(data: Any) -> tuple[Any, Any]:
+    """(counts2, counts4): the histograms ``block_order`` sorts at ``es`` 2
+    and at ``es`` 4, 256 int64 counts each. The numpy twin of
+    ``fpz_probe_kernel``."""
+    data = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
+    n = len(data)
+    return (
+        np.bincount(data[1 : n - n % 2 : 2], minlength=256),
+        np.bincount(data[3 : n - n % 4 : 4], minlength=256),
+    )
+
+
+def _estimate(counts: Any, raw_len: Any, es: int) -> Any:
+    """The estimate of ``choose_elem_size`` at ``es``, in int64: for one
+    table (256 counts, a scalar raw_len) or a table per row and as many
+    lengths."""
+    raw_len = np.asarray(raw_len, dtype=np.int64)
+    n = raw_len // es
+    # top[..., k - 1]: the k largest counts together
+    top = np.cumsum(-np.sort(-np.asarray(counts, dtype=np.int64), axis=-1), axis=-1)
+    hi = np.min(
+        [-(-n * b // 8) + n - top[..., (1 << b) - 2] for b in range(1, 8)], axis=0
+    )
+    return n * (es - 1) + hi + -(-raw_len // SEG_SIZE) + (raw_len - n * es)
+
+
+def _choose(counts2: Any, counts4: Any, raw_len: Any) -> tuple[Any, Any]:
+    e2, e4 = _estimate(counts2, raw_len, 2), _estimate(counts4, raw_len, 4)
+    est = np.minimum(e2, e4)
+    es = np.where(e2 <= e4, 2, 4)
+    return np.where(worth_keeping(est, np.asarray(raw_len, dtype=np.int64)), es, 0), est
+
+
+def choose_elem_size(counts2: Any, counts4: Any, raw_len: int) -> tuple[int, int]:
+    """(es, estimate): the element size at which MAFP10 would store a block
+    of ``raw_len`` bytes with these two histograms smaller, and the payload
+    estimated for it; ``es`` is 0 when even that misses
+    ``compress.worth_keeping``. Exact integer arithmetic, so the same tables
+    give the same answer anywhere.
+
+    For ``es`` in (2, 4), ``n = raw_len // es`` elements and the counts
+    sorted descending, the top bytes cost
+    ``hi = min over b in 1..7 of ceil(n*b/8) + (n - the 2^b - 1 largest counts)``
+    (codes at ONE width for the block plus the elements that width escapes) and
+    ``estimate = n*(es-1) + hi + n_seg + (raw_len - n*es)``: the low bytes, a
+    width byte per segment, the bytes of no whole element. 2 wins ties.
+
+    Why this bounds the encoder's payload. The escapes of a width summed over
+    the segments are the block's, and a full segment's ``m`` (2048 or 1024) is
+    a multiple of 8, so its code bytes at any width are exactly ``m*b/8``:
+    the segments coded all at the block's best width cost what the estimate
+    says. The encoder picks a width per segment, which can only cost less,
+    and stores a segment raw only when coding it would not be smaller. What
+    is left is the short last segment: its ``ceil`` can round up, and when its
+    length is no multiple of ``es`` it is stored raw, where the estimate coded
+    its whole elements. Either way the excess is less than ``SEG_SIZE``, and
+    there is none when ``raw_len`` is a multiple of 4. The estimate leaves out
+    the header and the segment table, as ``worth_keeping`` does."""
+    es, est = _choose(counts2, counts4, raw_len)
+    return int(es), int(est)
+
+
 def decompress_buffer_cpu(blob: bytes) -> bytes:
     """Raw bytes of a MAFP10 container; ValueError on a malformed header or
     a corrupt segment (the first one is named)."""
@@ -282,14 +358,43 @@ def workspace_for(raw_lens: Sequence[int]) -> Workspace:
     return Workspace(n_seg, len(raw_lens) * HEADER_FIXED + 4 * n_seg + sum(raw_lens))
 
 
+def probe_spans_gpu(lib: Any, base: int, spans: Sequence[tuple[int, int]]) -> tuple[list, Any]:
+    """``choose_elem_size`` for the device bytes ``(base + offset, raw_len)``
+    of every span: (the element size per span, 0 where MAFP10 would not pay;
+    the probe's tables, a ``len(spans) x 2 x 256`` int32 device tensor whose
+    ``[:, 0]`` and ``[:, 1]`` are the histograms at es 2 and 4). One probe
+    launch and one D2H of the tables (2 KiB per span) on the current stream;
+    the rule itself runs on the host, on the same tables as the numpy path."""
+    import torch
+
+    counts = torch.zeros(len(spans), 2, 256, dtype=torch.int32, device="cuda")
+    if not spans:
+        return [], counts
+    src_off_d = _to_dev(np.array([off for off, _ln in spans], dtype=np.int64))
+    raw_d = _to_dev(np.array([ln for _off, ln in spans], dtype=np.int64))
+    _check(
+        lib.ma_fpz_probe(
+            base, src_off_d.data_ptr(), raw_d.data_ptr(), counts.data_ptr(), len(spans),
+            torch.cuda.current_stream().cuda_stream,
+        ),
+        "fpz probe kernel",
+    )
+    host = counts.cpu().numpy().view(np.uint32)  # syncs: the tables may be freed
+    es, _est = _choose(host[:, 0], host[:, 1], [ln for _off, ln in spans])  # all spans at once
+    return es.tolist(), counts
+
+
 def compress_spans_gpu(
-    lib: Any, base: int, spans: Sequence[tuple[int, int]], es: int, ws: Workspace
+    lib: Any, base: int, spans: Sequence[tuple[int, int]], es: int, ws: Workspace,
+    counts: Any = None,
 ) -> list:
     """MAFP10 containers of the device bytes ``(base + offset, raw_len)`` per
     span, None where the container is not kept. One histogram, one rank, one
     encode and one plan launch for all spans, ONE sync (the per-span payload
     totals), one assemble launch and one D2H of the dense containers, all on
-    the current stream."""
+    the current stream. ``counts``, a contiguous ``len(spans) x 256`` int32
+    device tensor, is the spans' histograms at ``es`` where the caller has
+    them (``probe_spans_gpu``): the histogram launch is then left out."""
     import torch
 
     from .staging import copy_from_device
@@ -308,17 +413,25 @@ def compress_spans_gpu(
     first_d = _to_dev((ends_seg - n_segs).astype(np.int32))
     raw_d = _to_dev(raw_lens)
     src_off_d = _to_dev(np.array([off for off, _ln in spans], dtype=np.int64))
-    counts = torch.zeros(len(spans) * 256, dtype=torch.int32, device="cuda")
     tables = torch.empty(2, len(spans) * 256, dtype=torch.uint8, device="cuda")
     order_d, rank_d = tables[0], tables[1]
     payload_d = torch.empty(len(spans), dtype=torch.int64, device="cuda")
-    _check(
-        lib.ma_fpz_rank(
+    if counts is None:
+        counts = torch.zeros(len(spans) * 256, dtype=torch.int32, device="cuda")
+        rc = lib.ma_fpz_rank(
             base, src_off_d.data_ptr(), raw_d.data_ptr(), es, counts.data_ptr(),
             order_d.data_ptr(), rank_d.data_ptr(), len(spans), stream,
-        ),
-        "fpz histogram/rank kernels",
-    )
+        )
+    else:
+        if (
+            counts.dtype != torch.int32 or counts.numel() != len(spans) * 256
+            or not counts.is_cuda or not counts.is_contiguous()
+        ):
+            raise ValueError("counts is a contiguous int32 device tensor of len(spans) x 256")
+        rc = lib.ma_fpz_rank_counts(
+            counts.data_ptr(), order_d.data_ptr(), rank_d.data_ptr(), len(spans), stream
+        )
+    _check(rc, "fpz histogram/rank kernels")
     _check(
         lib.ma_fpz_encode(
             base, src_off_d.data_ptr(), raw_d.data_ptr(), first_d.data_ptr(),

@@ -309,7 +309,7 @@ def restore_payload(data: bytes, store: Any = None) -> dict:
 _RESTORE_CHUNK_BLOCKS = 8
 
 
-def capture_manifest(store: Any, float_codec: bool = False) -> bytes:
+def capture_manifest(store: Any, float_codec: Any = False) -> bytes:
     """Block-addressed snapshot: every registered tensor and tracked raw
     allocation is cut into CAS blocks, hashed and compressed where it lives
     (CUDA memory on the GPU through ops/devcodec.py, CPU tensors on the
@@ -317,16 +317,23 @@ def capture_manifest(store: Any, float_codec: bool = False) -> bytes:
     returned. Blocks the store already has are neither compressed nor
     copied, so a second snapshot of unchanged state costs its hashing.
 
-    ``float_codec`` offers the blocks of registered bf16/fp16/fp32 tensors
-    that LZ4 declined to the float-plane codec (ops/fpcodec.py). Raw
-    allocations carry no element type and are never offered. Digests are of
-    the raw blocks, so the manifest is the same either way, and restore
+    ``float_codec`` True offers the blocks of registered bf16/fp16/fp32
+    tensors that LZ4 declined to the float-plane codec (ops/fpcodec.py);
+    raw allocations carry no element type and are not offered. ``"auto"``
+    also offers everything else, the other registered tensors (CUDA or CPU)
+    and every tracked raw allocation, at the element size a probe of each
+    block's bytes finds, or raw where it finds none. Digests are of the raw
+    blocks, so the manifest is the same whatever the option, and restore
     needs no flag: a stored container names its codec."""
-    from ..ops import devcodec, rawmem
+    from ..ops import devcodec, fpcodec, rawmem
+
+    if float_codec not in (False, True, "auto"):
+        raise ValueError(f'float_codec is False, True or "auto", got {float_codec!r}')
+    untyped = fpcodec.AUTO if float_codec == "auto" else 0
 
     def hint(t: Any) -> int:
         fits = float_codec and t.dtype.is_floating_point and t.element_size() in (2, 4)
-        return t.element_size() if fits else 0
+        return t.element_size() if fits else untyped
 
     def entry_for(nbytes: int, **extra: Any) -> dict:
         return {"blocks": [], "block_lens": [], "nbytes": nbytes, **extra}
@@ -370,7 +377,7 @@ def capture_manifest(store: Any, float_codec: bool = False) -> bytes:
                 continue  # released (paged out) rows have no device memory
             entry = raw[key] = entry_for(found[1])
             if found[1]:
-                on_device.append((entry, found[0], found[1], 0, None))
+                on_device.append((entry, found[0], found[1], untyped, None))
     if on_device:
         objects = [(ptr, nbytes) for _e, ptr, nbytes, _es, _k in on_device]
         hints = [es for _e, _ptr, _n, es, _k in on_device]

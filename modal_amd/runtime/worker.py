@@ -195,13 +195,17 @@ class WorkerRPCTarget:
 
         return await asyncio.get_running_loop().run_in_executor(None, capture_payload)
 
-    async def snapshot_manifest(self, float_codec: bool = False) -> bytes:
+    async def snapshot_manifest(self, float_codec: Any = False) -> bytes:
         """Block-addressed snapshot (gpu_snapshot.capture_manifest): the
         state's blocks go straight into the shared CAS, encoded on the GPU
         where they live; only the small manifest crosses the socket.
-        ``float_codec`` offers float tensors to the float-plane codec."""
+        ``float_codec`` True offers float tensors to the float-plane codec,
+        ``"auto"`` also untyped tensors and tracked raw allocations."""
+        from ..exception import InvalidError
         from .gpu_snapshot import capture_manifest
 
+        if float_codec not in (False, True, "auto"):
+            raise InvalidError(f'float_codec is False, True or "auto", got {float_codec!r}')
         return await asyncio.get_running_loop().run_in_executor(
             None, capture_manifest, self._runtime.blob_store, float_codec
         )

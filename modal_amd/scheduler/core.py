@@ -1388,7 +1388,7 @@ class Scheduler:
 
     # -- worker GPU snapshots ---------------------------------------------
     async def worker_snapshot(
-        self, worker_id: int, block_addressed: bool = False, float_codec: bool = False
+        self, worker_id: int, block_addressed: bool = False, float_codec: Any = False
     ) -> dict:
         """Capture a worker's snapshot-visible GPU state (registered
         tensors + tracked raw hipMalloc allocations + RNG) into the CAS.
@@ -1400,14 +1400,18 @@ class Scheduler:
         of digests; unchanged blocks of a later snapshot are stored once.
 
         float_codec=True (needs block_addressed): blocks of float tensors
-        that LZ4 declined are stored as MAFP10 containers (ops/fpcodec.py)."""
+        that LZ4 declined are stored as MAFP10 containers (ops/fpcodec.py).
+        float_codec="auto" also offers the blocks of every other tensor and
+        of tracked raw allocations, at the element size found in their bytes."""
+        if float_codec not in (False, True, "auto"):
+            raise InvalidError(f'float_codec is False, True or "auto", got {float_codec!r}')
         if float_codec and not block_addressed:
             raise InvalidError("float_codec needs block_addressed=True")
         w = self.pool.workers.get(int(worker_id))
         if w is None:
             raise NotFoundError(f"worker {worker_id} not connected")
         rpc = "snapshot_manifest" if block_addressed else "snapshot_state"
-        params = {"float_codec": True} if float_codec else None
+        params = {"float_codec": float_codec} if float_codec else None
         data = await w.conn.call(rpc, params, timeout=300)
         blob_id = self.blob_store.put(data)
         return {"snapshot_id": blob_id}
