@@ -2,6 +2,7 @@
 
 from __future__ import annotations
 
+import functools
 import os
 import random
 
@@ -199,7 +200,7 @@ def test_put_many_batched_compression_roundtrip():
 
 
 @pytest.mark.gpu
-def test_pipelined_put_many_bit_identical():
+def test_pipelined_put_many_bit_identical(monkeypatch):
     """The pipelined window path (ops/pipeline.py) produces the same CAS
     keys and round-trips the same bytes as the serial path."""
     import tempfile
@@ -230,6 +231,23 @@ def test_pipelined_put_many_bit_identical():
     assert digests_pipelined == digests_serial
     for digest, block in zip(digests_pipelined, blocks):
         assert store_a.get(digest) == block
+
+    # and against the host, which shares nothing with either GPU path: the
+    # host tree hash, and the host codec over utils/lz4ref.py, whose parser is
+    # the kernel's (the C++ core is another LZ4 parser: other bytes). The
+    # blocks are periodic, so a segment's block is computed once per phase.
+    from modal_amd.ops.hashing import content_digest
+
+    monkeypatch.setattr(C, "_native_core", lambda: None)
+    monkeypatch.setattr(lz4ref, "compress_block", functools.lru_cache(maxsize=None)(lz4ref.compress_block))
+    n_compressed = 0
+    for i, (digest, block) in enumerate(zip(digests_pipelined, blocks)):
+        assert digest == content_digest(block, gpu=False), f"block {i}"
+        payload, compressed = store_a.get_stored(digest)
+        if compressed:
+            n_compressed += 1
+            assert payload == C.compress_buffer_cpu(block), f"block {i}"
+    assert n_compressed == 13
 
 
 def test_native_codec_cross_compatible_with_reference_codec():

@@ -5,6 +5,7 @@ from __future__ import annotations
 import hashlib
 import random
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -47,10 +48,11 @@ def test_tree_sha256_gpu_matches_cpu():
     _require_gpu()
     from modal_amd.ops.hashing import _tree_sha256_gpu, tree_sha256_cpu
 
-    rng = random.Random(3)
+    # not periodic: with equal leaves the root would not see leaves hashed
+    # from the wrong offset or stored in the wrong order
+    rng = np.random.default_rng(3)
     for size in [8 * 1024 * 1024, 8 * 1024 * 1024 + 12345, 32 * 1024 * 1024 + 7]:
-        data = bytes(rng.randrange(256) for _ in range(1024)) * (size // 1024)
-        data = data[:size]
+        data = rng.integers(0, 256, size, dtype=np.uint8).tobytes()
         assert _tree_sha256_gpu(data) == tree_sha256_cpu(data)
 
 
@@ -134,7 +136,8 @@ def test_blobstore_uses_gpu_hash(tmp_path):
     from modal_amd.scheduler.blobs import BlobStore
 
     store = BlobStore(str(tmp_path / "blobs"))
-    data = bytes(bytearray(range(256)) * (40 * 1024))  # 10 MiB -> tree/GPU path
+    # 10 MiB -> tree/GPU path; no two leaves alike
+    data = np.random.default_rng(5).integers(0, 256, 10 * 1024 * 1024, dtype=np.uint8).tobytes()
     digest = store.put(data)
     assert digest == tree_sha256_cpu(data).hex()
     assert store.get(digest) == data
@@ -148,7 +151,7 @@ def test_content_digests_batch_gpu_matches_cpu():
 
     buffers = [_os.urandom(9 * 1024 * 1024), b"small", _os.urandom(8 * 1024 * 1024), b""]
     got = content_digests_batch(buffers)
-    expect = [content_digest(b) for b in buffers]
+    expect = [content_digest(b, gpu=False) for b in buffers]  # the host tree hash
     assert got == expect
 
 
