@@ -340,10 +340,6 @@ extern "C" __global__ __launch_bounds__(WAVE) void fpz_encode_kernel(
 // assemble
 // ---------------------------------------------------------------------------
 
-#define ASM_BLOCK 256
-#define ASM_WAVES (ASM_BLOCK / WAVE)
-#define ASM_GROUPS 512
-
 extern "C" __global__ __launch_bounds__(ASM_BLOCK) void fpz_assemble_kernel(
     const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_src_off,
     const uint8_t* __restrict__ stride_buf, int out_stride,
@@ -354,14 +350,12 @@ extern "C" __global__ __launch_bounds__(ASM_BLOCK) void fpz_assemble_kernel(
   const int b = blk_base + blockIdx.y;
   const int64_t out_off = blk_out_off[b];
   if (out_off < 0) return;  // container not kept: nothing to assemble
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
   const int64_t raw_len = blk_raw_len[b];
   const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
-  const int64_t first = blk_first_seg[b];
   uint8_t* blk_out = out + out_off;
 
-  if (blockIdx.x == 0 && wave == 0) {
+  if (blockIdx.x == 0 && threadIdx.x < WAVE) {
+    const int lane = threadIdx.x;
     const uint64_t magic = 0x30315046414DULL;  // "MAFP10", little-endian
     put_le(blk_out, magic, 6, lane);
     put_le(blk_out + 6, (uint64_t)raw_len, 8, lane);
@@ -369,17 +363,8 @@ extern "C" __global__ __launch_bounds__(ASM_BLOCK) void fpz_assemble_kernel(
     put_le(blk_out + 16, (uint64_t)n_seg, 4, lane);
     wave_copy(order + (int64_t)b * 256, blk_out + 20, 256, lane);
   }
-  uint8_t* table = blk_out + FPZ_HEADER_FIXED;
-  uint8_t* payload = table + 4 * n_seg;
-  const uint8_t* blk_src = src + blk_src_off[b];
-  for (int64_t s = (int64_t)blockIdx.x * ASM_WAVES + wave; s < n_seg;
-       s += (int64_t)gridDim.x * ASM_WAVES) {
-    const int clen = comp_lens[first + s];
-    put_le(table + 4 * s, (uint32_t)clen, 4, lane);
-    const uint8_t* from = clen ? stride_buf + (first + s) * out_stride
-                               : blk_src + s * SEG_SIZE;
-    wave_copy(from, payload + seg_off[first + s], seg_eff(clen, raw_len, s), lane);
-  }
+  assemble_segments(blk_out + FPZ_HEADER_FIXED, src + blk_src_off[b], stride_buf, out_stride,
+                    comp_lens, seg_off, blk_first_seg[b], raw_len, n_seg);
 }
 
 // ---------------------------------------------------------------------------
@@ -504,42 +489,6 @@ extern "C" __global__ __launch_bounds__(WAVE) void fpz_decode_kernel(
 // host entry points
 // ---------------------------------------------------------------------------
 
-// counts (n_blocks x 256 u32) must come in zeroed.
-extern "C" int ma_fpz_rank(const void* src, const void* blk_src_off, const void* blk_raw_len,
-                           int es, void* counts, void* order, void* rank_of, int n_blocks,
-                           void* stream) {
-  if (n_blocks <= 0) return 0;
-  if (es != 2 && es != 4) return (int)hipErrorInvalidValue;
-  for (int base = 0; base < n_blocks; base += MAX_GRID_Y) {
-    int ny = n_blocks - base < MAX_GRID_Y ? n_blocks - base : MAX_GRID_Y;
-    hipLaunchKernelGGL(fpz_hist_kernel, dim3(HIST_GROUPS, ny), dim3(HIST_BLOCK), 0,
-                       (hipStream_t)stream, (const uint8_t*)src,
-                       (const int64_t*)blk_src_off, (const int64_t*)blk_raw_len, es,
-                       (uint32_t*)counts, base);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
-  }
-  hipLaunchKernelGGL(fpz_rank_kernel, dim3(n_blocks), dim3(256), 0, (hipStream_t)stream,
-                     (const uint32_t*)counts, (uint8_t*)order, (uint8_t*)rank_of);
-  return (int)hipGetLastError();
-}
-
-// counts (n_blocks x 2 x 256 u32) must come in zeroed: [b][0] the es = 2
-// histogram of block b, [b][1] the es = 4 one.
-extern "C" int ma_fpz_probe(const void* src, const void* blk_src_off, const void* blk_raw_len,
-                            void* counts, int n_blocks, void* stream) {
-  for (int base = 0; base < n_blocks; base += MAX_GRID_Y) {
-    int ny = n_blocks - base < MAX_GRID_Y ? n_blocks - base : MAX_GRID_Y;
-    hipLaunchKernelGGL(fpz_probe_kernel, dim3(PROBE_GROUPS, ny), dim3(PROBE_BLOCK), 0,
-                       (hipStream_t)stream, (const uint8_t*)src,
-                       (const int64_t*)blk_src_off, (const int64_t*)blk_raw_len,
-                       (uint32_t*)counts, base);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
-  }
-  return 0;
-}
-
 // The rank tables of histograms the caller already has (n_blocks x 256 u32,
 // a probe's for instance): ma_fpz_rank without its histogram pass.
 extern "C" int ma_fpz_rank_counts(const void* counts, void* order, void* rank_of, int n_blocks,
@@ -550,6 +499,33 @@ extern "C" int ma_fpz_rank_counts(const void* counts, void* order, void* rank_of
   return (int)hipGetLastError();
 }
 
+// counts (n_blocks x 256 u32) must come in zeroed.
+extern "C" int ma_fpz_rank(const void* src, const void* blk_src_off, const void* blk_raw_len,
+                           int es, void* counts, void* order, void* rank_of, int n_blocks,
+                           void* stream) {
+  if (n_blocks <= 0) return 0;
+  if (es != 2 && es != 4) return (int)hipErrorInvalidValue;
+  const int rc = launch_chunked(n_blocks, [&](int base, int ny) {
+    hipLaunchKernelGGL(fpz_hist_kernel, dim3(HIST_GROUPS, ny), dim3(HIST_BLOCK), 0,
+                       (hipStream_t)stream, (const uint8_t*)src,
+                       (const int64_t*)blk_src_off, (const int64_t*)blk_raw_len, es,
+                       (uint32_t*)counts, base);
+  });
+  return rc ? rc : ma_fpz_rank_counts(counts, order, rank_of, n_blocks, stream);
+}
+
+// counts (n_blocks x 2 x 256 u32) must come in zeroed: [b][0] the es = 2
+// histogram of block b, [b][1] the es = 4 one.
+extern "C" int ma_fpz_probe(const void* src, const void* blk_src_off, const void* blk_raw_len,
+                            void* counts, int n_blocks, void* stream) {
+  return launch_chunked(n_blocks, [&](int base, int ny) {
+    hipLaunchKernelGGL(fpz_probe_kernel, dim3(PROBE_GROUPS, ny), dim3(PROBE_BLOCK), 0,
+                       (hipStream_t)stream, (const uint8_t*)src,
+                       (const int64_t*)blk_src_off, (const int64_t*)blk_raw_len,
+                       (uint32_t*)counts, base);
+  });
+}
+
 // max_segs: the largest segment count of any block (bounds the grid).
 extern "C" int ma_fpz_encode(const void* src, const void* blk_src_off,
                              const void* blk_raw_len, const void* blk_first_seg,
@@ -558,17 +534,13 @@ extern "C" int ma_fpz_encode(const void* src, const void* blk_src_off,
   if (n_blocks <= 0 || max_segs <= 0) return 0;
   if (es != 2 && es != 4) return (int)hipErrorInvalidValue;
   const int gx = (int)(max_segs < 16384 ? max_segs : 16384);
-  for (int base = 0; base < n_blocks; base += MAX_GRID_Y) {
-    int ny = n_blocks - base < MAX_GRID_Y ? n_blocks - base : MAX_GRID_Y;
+  return launch_chunked(n_blocks, [&](int base, int ny) {
     hipLaunchKernelGGL(fpz_encode_kernel, dim3(gx, ny), dim3(WAVE), 0, (hipStream_t)stream,
                        (const uint8_t*)src, (const int64_t*)blk_src_off,
                        (const int64_t*)blk_raw_len, (const int32_t*)blk_first_seg,
                        (const uint8_t*)rank_of, es, (uint8_t*)stride_buf, out_stride,
                        (int32_t*)comp_lens, base);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
-  }
-  return 0;
+  });
 }
 
 extern "C" int ma_fpz_assemble(const void* src, const void* blk_src_off,
@@ -578,8 +550,7 @@ extern "C" int ma_fpz_assemble(const void* src, const void* blk_src_off,
                                const void* order, int es, void* out,
                                const void* blk_out_off, int n_blocks, void* stream) {
   if (es != 2 && es != 4) return (int)hipErrorInvalidValue;
-  for (int base = 0; base < n_blocks; base += MAX_GRID_Y) {
-    int ny = n_blocks - base < MAX_GRID_Y ? n_blocks - base : MAX_GRID_Y;
+  return launch_chunked(n_blocks, [&](int base, int ny) {
     hipLaunchKernelGGL(fpz_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
                        (hipStream_t)stream, (const uint8_t*)src,
                        (const int64_t*)blk_src_off, (const uint8_t*)stride_buf, out_stride,
@@ -587,10 +558,7 @@ extern "C" int ma_fpz_assemble(const void* src, const void* blk_src_off,
                        (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
                        (const uint8_t*)order, es, (uint8_t*)out,
                        (const int64_t*)blk_out_off, base);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
-  }
-  return 0;
+  });
 }
 
 extern "C" int ma_fpz_decode(const void* comp, const void* comp_offs, const void* dst_offs,

@@ -11,9 +11,9 @@
 //   plan      per block: eff[i] = comp_len ? comp_len : raw segment length,
 //             exclusive scan -> seg_off, sum -> blk_payload (the host's
 //             keep/raw decision needs only that one int64 per block)
-//   assemble  per kept block: header + comp_len table + every segment's
-//             bytes at 18 + 4*n_seg + seg_off[s], compressed segments from
-//             their stride slot, raw ones from the source
+//   assemble  per kept block: header, then comp_len table + every segment's
+//             bytes at 18 + 4*n_seg + seg_off[s] (assemble_segments in
+//             malz_common.h, which fpz.hip's assemble kernel shares)
 //
 // Segment arrays (comp_lens, seg_off, stride slots) are indexed by
 // blk_first_seg[b] + s; a block's segment count is ceil(blk_raw_len[b]/4096).
@@ -23,9 +23,6 @@
 #include "malz_common.h"
 
 #define PLAN_BLOCK 256
-#define ASM_BLOCK 256
-#define ASM_WAVES (ASM_BLOCK / WAVE)  // one wavefront per segment
-#define ASM_GROUPS 512                // x 4 waves = the 2048 segments of 8 MiB
 #define HEADER_FIXED 18               // magic(6) + u64 raw_len + u32 n_seg
 
 extern "C" __global__ __launch_bounds__(PLAN_BLOCK) void malz_plan_kernel(
@@ -88,30 +85,19 @@ extern "C" __global__ __launch_bounds__(ASM_BLOCK) void malz_assemble_kernel(
   const int b = blk_base + blockIdx.y;
   const int64_t out_off = blk_out_off[b];
   if (out_off < 0) return;  // block stored raw: nothing to assemble
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
   const int64_t raw_len = blk_raw_len[b];
   const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
-  const int64_t first = blk_first_seg[b];
   uint8_t* blk_out = out + out_off;
 
-  if (blockIdx.x == 0 && wave == 0) {
+  if (blockIdx.x == 0 && threadIdx.x < WAVE) {
+    const int lane = threadIdx.x;
     const uint64_t magic = 0x31345A4C414DULL;  // "MALZ41", little-endian
     put_le(blk_out, magic, 6, lane);
     put_le(blk_out + 6, (uint64_t)raw_len, 8, lane);
     put_le(blk_out + 14, (uint64_t)n_seg, 4, lane);
   }
-  uint8_t* table = blk_out + HEADER_FIXED;
-  uint8_t* payload = table + 4 * n_seg;
-  const uint8_t* blk_src = src + blk_src_off[b];
-  for (int64_t s = (int64_t)blockIdx.x * ASM_WAVES + wave; s < n_seg;
-       s += (int64_t)gridDim.x * ASM_WAVES) {
-    const int clen = comp_lens[first + s];
-    put_le(table + 4 * s, (uint32_t)clen, 4, lane);
-    const uint8_t* from = clen ? stride_buf + (first + s) * out_stride
-                               : blk_src + s * SEG_SIZE;
-    wave_copy(from, payload + seg_off[first + s], seg_eff(clen, raw_len, s), lane);
-  }
+  assemble_segments(blk_out + HEADER_FIXED, src + blk_src_off[b], stride_buf, out_stride,
+                    comp_lens, seg_off, blk_first_seg[b], raw_len, n_seg);
 }
 
 extern "C" int ma_malz_plan(const void* comp_lens, const void* blk_first_seg,
@@ -131,18 +117,14 @@ extern "C" int ma_malz_assemble(const void* src, const void* blk_src_off,
                                 const void* blk_first_seg, const void* blk_raw_len,
                                 void* out, const void* blk_out_off, int n_blocks,
                                 void* stream) {
-  for (int base = 0; base < n_blocks; base += MAX_GRID_Y) {
-    int ny = n_blocks - base < MAX_GRID_Y ? n_blocks - base : MAX_GRID_Y;
+  return launch_chunked(n_blocks, [&](int base, int ny) {
     hipLaunchKernelGGL(malz_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
                        (hipStream_t)stream, (const uint8_t*)src,
                        (const int64_t*)blk_src_off, (const uint8_t*)stride_buf, out_stride,
                        (const int32_t*)comp_lens, (const int64_t*)seg_off,
                        (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
                        (uint8_t*)out, (const int64_t*)blk_out_off, base);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
-  }
-  return 0;
+  });
 }
 
 // Async copy on the caller's stream for the raw-pointer codec (ops/devcodec.py):

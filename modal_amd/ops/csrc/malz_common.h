@@ -1,5 +1,6 @@
-// Device helpers shared by the container kernels (malz.hip, fpz.hip) for
-// gfx950: the raw length of a segment and byte-exact wavefront copies.
+// Shared by the container kernels (malz.hip, fpz.hip) for gfx950: the raw
+// length of a segment, byte-exact wavefront copies, the segment table and
+// payload of a container, the launch loop for grids past MAX_GRID_Y rows.
 
 #pragma once
 
@@ -9,6 +10,9 @@
 #define SEG_SIZE 4096
 #define WAVE 64
 #define MAX_GRID_Y 65535
+#define ASM_BLOCK 256
+#define ASM_WAVES (ASM_BLOCK / WAVE)  // one wavefront per segment
+#define ASM_GROUPS 512                // x 4 waves = the 2048 segments of 8 MiB
 
 __device__ __forceinline__ int seg_eff(int clen, int64_t raw_len, int64_t s) {
   if (clen) return clen;
@@ -64,4 +68,38 @@ __device__ void wave_copy(const uint8_t* __restrict__ src, uint8_t* __restrict__
 
 __device__ __forceinline__ void put_le(uint8_t* dst, uint64_t v, int nbytes, int lane) {
   if (lane < nbytes) dst[lane] = (uint8_t)(v >> (8 * lane));
+}
+
+// What follows a container's fixed header, for one block of an assemble grid
+// (ASM_GROUPS x blocks, ASM_BLOCK threads): the comp_len table at `table` and
+// behind it every segment's bytes at its seg_off, compressed segments from
+// their stride slot (indexed, like comp_lens and seg_off, from `first`), raw
+// ones from the source.
+__device__ __forceinline__ void assemble_segments(
+    uint8_t* table, const uint8_t* __restrict__ blk_src, const uint8_t* __restrict__ stride_buf,
+    int out_stride, const int32_t* __restrict__ comp_lens, const int64_t* __restrict__ seg_off,
+    int64_t first, int64_t raw_len, int64_t n_seg) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  uint8_t* payload = table + 4 * n_seg;
+  for (int64_t s = (int64_t)blockIdx.x * ASM_WAVES + wave; s < n_seg;
+       s += (int64_t)gridDim.x * ASM_WAVES) {
+    const int clen = comp_lens[first + s];
+    put_le(table + 4 * s, (uint32_t)clen, 4, lane);
+    const uint8_t* from = clen ? stride_buf + (first + s) * out_stride
+                               : blk_src + s * SEG_SIZE;
+    wave_copy(from, payload + seg_off[first + s], seg_eff(clen, raw_len, s), lane);
+  }
+}
+
+// A grid of n_blocks rows in chunks of at most MAX_GRID_Y: launch(base, ny)
+// starts the kernel for rows [base, base + ny). Returns the first HIP error.
+template <typename Launch>
+static inline int launch_chunked(int n_blocks, Launch launch) {
+  for (int base = 0; base < n_blocks; base += MAX_GRID_Y) {
+    launch(base, n_blocks - base < MAX_GRID_Y ? n_blocks - base : MAX_GRID_Y);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return (int)err;
+  }
+  return 0;
 }

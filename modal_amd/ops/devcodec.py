@@ -7,15 +7,16 @@ raw allocation) is encoded where it is: split into CAS blocks of
 handed to ``compress.compress_spans_gpu``, the one device encoder, which also
 serves ``BlobStore.put``. Only the dense containers, or the raw bytes of
 blocks that do not compress, cross to the host. Decoding validates every
-container header on the host (``compress.validate_container``), stages the
-compressed bytes H2D and decompresses straight into the destination
-allocation through ``compress.decompress_run_gpu``.
+container header on the host, stages the compressed bytes H2D and decompresses
+straight into the destination allocation, with ``validate_container`` and
+``decompress_run_gpu`` of the codec the magic selects (``compress.codec_of``).
 
 An object the caller hints as float data (``elem_size`` 2 or 4) offers the
 blocks LZ4 declined to the float-plane codec (ops/fpcodec.py, MAFP10); an
 object of no known element type (``fpcodec.AUTO``) has those blocks probed on
-the device for the element size at which the codec pays, if any. A stored
-container's magic selects its validator and decoder.
+the device for the element size at which the codec pays, if any. Both
+codecs stand on ops/container.py and both validators return headers that
+begin (raw_len, seg lens, payload offset): nothing here tells them apart.
 
 What this module adds to those is the block layer: digests, skipping blocks
 the CAS already has, the cached 64 MiB scratch with its out-of-memory
@@ -37,7 +38,7 @@ import numpy as np
 
 from ..scheduler.blobs import BLOCK_SIZE, BlobStore
 from . import compress, fpcodec, load_lib
-from .compress import SEG_SIZE
+from .container import SEG_SIZE, Workspace
 from .hashing import GPU_MIN_BYTES, content_digest, leaf_table, sha256_leaves_gpu, tree_roots
 from .staging import copy_from_device, copy_to_device
 
@@ -62,14 +63,14 @@ _codec_lock = threading.Lock()  # the scratch below is shared
 _scratch: Any = None
 
 
-def _get_scratch() -> Optional[compress.Workspace]:
+def _get_scratch() -> Optional[Workspace]:
     """Strided compress output (1.0625x the window) + dense containers (the
     window) + per-segment tables: ~135 MiB of HBM, allocated once. None when
     HBM cannot spare it: the caller then stores raw blocks."""
     global _scratch
     if _scratch is None:
         try:
-            _scratch = compress.Workspace(WINDOW // SEG_SIZE, WINDOW)
+            _scratch = Workspace(WINDOW // SEG_SIZE, WINDOW)
         except RuntimeError:  # torch.OutOfMemoryError is one
             return None
     return _scratch
@@ -163,7 +164,7 @@ def _check_block_size(block_size: int) -> None:
 
 
 def _encode_window(
-    lib: Any, sc: compress.Workspace, ptr: int, spans: Sequence[tuple[int, int]],
+    lib: Any, sc: Workspace, ptr: int, spans: Sequence[tuple[int, int]],
     digests: list, known: Optional[Callable[[str], bool]], elem_size: int = 0,
 ) -> list[EncodedBlock]:
     """Blocks of one window (<= WINDOW source bytes) of the object at ptr.
@@ -291,11 +292,11 @@ def encode_tensor(
 # ---------------------------------------------------------------------------
 
 
-def validate_container(payload: bytes, raw_len: int, index: int) -> tuple:
-    """The validator the container's magic selects (``compress`` or
-    ``fpcodec``) against the manifest's raw_len; the ValueError names block
-    ``index``. What it returns starts (raw_len, seg lens, payload offset)."""
-    codec = fpcodec if fpcodec.is_fp_container(payload) else compress
+def validate_container(payload: bytes, raw_len: int, index: int, codec: Any = None) -> tuple:
+    """The header of a stored container, (raw_len, seg lens, payload offset,
+    ...), from the validator of ``codec`` (``compress.codec_of`` when not
+    given) against the manifest's raw_len; the ValueError names block ``index``."""
+    codec = codec or compress.codec_of(payload)
     return codec.validate_container(payload, raw_len, f"snapshot block {index}")
 
 
@@ -316,27 +317,27 @@ def decode_to_device(blocks: Sequence, ptr: int, nbytes: int, *, verify: bool = 
     of device memory at ``ptr``. Every container header is validated against
     the manifest before anything is launched."""
     _check_layout(blocks, nbytes)
-    parsed: dict[int, tuple] = {}
+    parsed: dict[int, tuple] = {}  # block -> (codec, header)
     for i, (_d, raw_len, payload, compressed) in enumerate(blocks):
         if compressed:
-            parsed[i] = validate_container(payload, raw_len, i)
+            codec = compress.codec_of(payload)
+            parsed[i] = codec, validate_container(payload, raw_len, i, codec)
     if not blocks:
         return
     lib = load_lib(required=True)
     import torch
 
     offs = np.concatenate([[0], np.cumsum([b[1] for b in blocks])]).astype(np.int64)
-    # maximal runs of consecutive compressed blocks of one kind, cut to the
+    # maximal runs of consecutive compressed blocks of one codec, cut to the
     # staging window
-    is_fp = {i: isinstance(p, fpcodec.Header) for i, p in parsed.items()}
     runs: list[list[int]] = []
     staged = 0
     for i in range(len(blocks)):
         if i not in parsed:
             continue
-        size = len(blocks[i][2]) - parsed[i][2]
+        size = len(blocks[i][2]) - parsed[i][1].payload_off
         if (
-            runs and runs[-1][-1] == i - 1 and is_fp[i - 1] == is_fp[i]
+            runs and runs[-1][-1] == i - 1 and parsed[i - 1][0] is parsed[i][0]
             and len(runs[-1]) < RUN_MAX_BLOCKS and staged + size <= WINDOW
         ):
             runs[-1].append(i)
@@ -346,13 +347,11 @@ def decode_to_device(blocks: Sequence, ptr: int, nbytes: int, *, verify: bool = 
             staged = size
     with _codec_lock:
         for run in runs:
-            parts = [memoryview(blocks[i][2])[parsed[i][2] :] for i in run]
+            codec = parsed[run[0]][0]
+            parts = [memoryview(blocks[i][2])[parsed[i][1].payload_off :] for i in run]
             comp = torch.empty(sum(len(p) for p in parts), dtype=torch.uint8, device="cuda")
             copy_to_device(comp.data_ptr(), parts)
-            if is_fp[run[0]]:
-                codec, headers = fpcodec, [parsed[i] for i in run]
-            else:
-                codec, headers = compress, [parsed[i][:2] for i in run]
+            headers = [parsed[i][1] for i in run]
             bad = codec.decompress_run_gpu(lib, comp.data_ptr(), headers, ptr + int(offs[run[0]]))
             if bad:
                 raise ValueError(

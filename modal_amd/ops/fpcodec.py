@@ -29,33 +29,31 @@ pad bits; then the raw top byte of every element whose code is the escape
 the escape. ``b`` minimises hi = 1 + ceil(m*b/8) + n_escapes(b), smallest b
 on ties; the segment is coded only if L % es == 0 and hi < m, so
 seg_len = m*(es-1) + hi < L. The container is kept under the one 5 % rule,
-``compress.worth_keeping``.
+``container.worth_keeping``.
 
 A caller that does not know ``es`` (untyped device memory) asks the bytes:
 the probe gives the block's top-byte histograms at both element sizes and
 ``choose_elem_size`` picks the one at which the container comes out smaller,
 or none.
 
-Everything that touches the format lives here once: the validator, the
-numpy codec (the model the kernels in csrc/fpz.hip are held to byte for
-byte, and the reader of GPU-less processes), the device encoder and the
-device decoder launch. ``seg_len`` means what MALZ41's ``comp_len`` means, so
-``compress.effective_lens``, the plan kernel and ``compress.Workspace`` serve
-unchanged.
+What only MAFP10 knows lives here once: its header fields and their checks,
+the numpy codec (the model the kernels in csrc/fpz.hip are held to byte for
+byte, and the reader of GPU-less processes), the probe and its rule, the
+device encoder's launches up to the stride slots and the decode launch.
+``seg_len`` means what MALZ41's ``comp_len`` means, so the segmented
+container under both is one layer, ops/container.py.
 """
 
 from __future__ import annotations
 
 import struct
+import sys
 from typing import Any, NamedTuple, Optional, Sequence
 
 import numpy as np
 
-from . import gpu_available, load_lib
-from .compress import (
-    _STATUS_CLEAN, OUT_STRIDE, SEG_SIZE, Workspace, _check, _to_dev, effective_lens,
-    worth_keeping,
-)
+from . import container, gpu_available, load_lib
+from .container import OUT_STRIDE, SEG_SIZE, Workspace, effective_lens, seg_raw_lens, worth_keeping
 
 MAGIC = b"MAFP10"
 ELEM_SIZES = (2, 4)
@@ -74,52 +72,40 @@ def is_fp_container(blob: bytes) -> bool:
     return bytes(blob[: len(MAGIC)]) == MAGIC
 
 
-def _seg_raw(n_seg: int, raw_len: int) -> Any:
-    """Raw length L of every segment (int64 array)."""
-    L = np.full(n_seg, SEG_SIZE, dtype=np.int64)
-    if n_seg:
-        L[-1] = raw_len - (n_seg - 1) * SEG_SIZE
-    return L
-
-
 def validate_container(
     blob: bytes, raw_len: Optional[int] = None, what: str = "container"
 ) -> Header:
     """Parse a MAFP10 container and bound everything a decoder indexes with.
     Raises ValueError naming ``what``."""
 
-    def bad(why: str) -> ValueError:
-        return ValueError(f"{what}: {why}")
+    es, order = 0, None  # set by the two checks that run inside the shared reader
 
-    n = len(blob)
-    if n < HEADER_FIXED or not is_fp_container(blob):
-        raise bad("not a MAFP10 container")
-    hdr_raw, es, reserved, n_seg = struct.unpack_from("<QBBI", blob, len(MAGIC))
-    if es not in ELEM_SIZES:
-        raise bad(f"element size {es} is not 2 or 4")
-    if reserved != 0:
-        raise bad("reserved byte is not 0")
-    if raw_len is not None and hdr_raw != raw_len:
-        raise bad(f"container raw_len {hdr_raw} != manifest {raw_len}")
-    if n_seg != -(-hdr_raw // SEG_SIZE):
-        raise bad(f"container has {n_seg} segments for {hdr_raw} bytes")
-    order = np.frombuffer(blob, dtype=np.uint8, count=256, offset=HEADER_FIXED - 256)
-    if not np.array_equal(np.sort(order), np.arange(256, dtype=np.uint8)):
-        raise bad("order table is not a permutation")
-    off = HEADER_FIXED + 4 * n_seg
-    if n < off:
-        raise bad("container truncated inside its segment table")
-    seg_lens = np.frombuffer(blob, dtype="<u4", count=n_seg, offset=HEADER_FIXED).astype(np.int64)
-    L = _seg_raw(n_seg, hdr_raw)
+    def elem_fields() -> None:
+        nonlocal es
+        es, reserved = struct.unpack_from("<BB", blob, len(MAGIC) + 8)
+        if es not in ELEM_SIZES:
+            raise ValueError(f"{what}: element size {es} is not 2 or 4")
+        if reserved != 0:
+            raise ValueError(f"{what}: reserved byte is not 0")
+
+    def order_table() -> None:
+        nonlocal order
+        order = np.frombuffer(blob, dtype=np.uint8, count=256, offset=HEADER_FIXED - 256)
+        if not np.array_equal(np.sort(order), np.arange(256, dtype=np.uint8)):
+            raise ValueError(f"{what}: order table is not a permutation")
+
+    hdr_raw, n_seg, seg_lens, off = container.read_header(
+        blob, raw_len, what, MAGIC, HEADER_FIXED, len(MAGIC) + 10, elem_fields, order_table
+    )
+    seg_lens = seg_lens.astype(np.int64)
+    L = seg_raw_lens(n_seg, hdr_raw)
     coded = seg_lens != 0
     if np.any(coded & (L % es != 0)):
-        raise bad("coded segment is not a whole number of elements")
+        raise ValueError(f"{what}: coded segment is not a whole number of elements")
     lo = (L // es) * (es - 1)
     if np.any(coded & ((seg_lens < lo + 2) | (seg_lens >= L))):
-        raise bad("segment seg_len out of range")
-    payload = int(np.where(coded, seg_lens, L).sum())
-    if off + payload != n:
-        raise bad(f"container is {n} bytes, header says {off + payload}")
+        raise ValueError(f"{what}: segment seg_len out of range")
+    container.check_size(blob, off, int(np.where(coded, seg_lens, L).sum()), what)
     return Header(hdr_raw, seg_lens.astype(np.int32), off, es, order)
 
 
@@ -271,7 +257,7 @@ def choose_elem_size(counts2: Any, counts4: Any, raw_len: int) -> tuple[int, int
     """(es, estimate): the element size at which MAFP10 would store a block
     of ``raw_len`` bytes with these two histograms smaller, and the payload
     estimated for it; ``es`` is 0 when even that misses
-    ``compress.worth_keeping``. Exact integer arithmetic, so the same tables
+    ``container.worth_keeping``. Exact integer arithmetic, so the same tables
     give the same answer anywhere.
 
     For ``es`` in (2, 4), ``n = raw_len // es`` elements and the counts
@@ -304,7 +290,7 @@ def decompress_buffer_cpu(blob: bytes) -> bytes:
     buf = np.frombuffer(blob, dtype=np.uint8)
     out = np.empty(n, dtype=np.uint8)
     seg_lens = hdr.seg_lens.astype(np.int64)
-    L_of = _seg_raw(len(seg_lens), n)
+    L_of = seg_raw_lens(len(seg_lens), n)
     eff = effective_lens(seg_lens, n)
     offs = hdr.payload_off + np.cumsum(eff) - eff
     for s in np.flatnonzero(seg_lens == 0):
@@ -352,12 +338,6 @@ def decompress_buffer_cpu(blob: bytes) -> bytes:
 # ---------------------------------------------------------------------------
 
 
-def workspace_for(raw_lens: Sequence[int]) -> Workspace:
-    """A ``compress.Workspace`` sized to one ``compress_spans_gpu`` call."""
-    n_seg = sum(-(-n // SEG_SIZE) for n in raw_lens)
-    return Workspace(n_seg, len(raw_lens) * HEADER_FIXED + 4 * n_seg + sum(raw_lens))
-
-
 def probe_spans_gpu(lib: Any, base: int, spans: Sequence[tuple[int, int]]) -> tuple[list, Any]:
     """``choose_elem_size`` for the device bytes ``(base + offset, raw_len)``
     of every span: (the element size per span, 0 where MAFP10 would not pay;
@@ -370,9 +350,9 @@ def probe_spans_gpu(lib: Any, base: int, spans: Sequence[tuple[int, int]]) -> tu
     counts = torch.zeros(len(spans), 2, 256, dtype=torch.int32, device="cuda")
     if not spans:
         return [], counts
-    src_off_d = _to_dev(np.array([off for off, _ln in spans], dtype=np.int64))
-    raw_d = _to_dev(np.array([ln for _off, ln in spans], dtype=np.int64))
-    _check(
+    src_off_d = container.to_dev(np.array([off for off, _ln in spans], dtype=np.int64))
+    raw_d = container.to_dev(np.array([ln for _off, ln in spans], dtype=np.int64))
+    container.check(
         lib.ma_fpz_probe(
             base, src_off_d.data_ptr(), raw_d.data_ptr(), counts.data_ptr(), len(spans),
             torch.cuda.current_stream().cuda_stream,
@@ -389,33 +369,26 @@ def compress_spans_gpu(
     counts: Any = None,
 ) -> list:
     """MAFP10 containers of the device bytes ``(base + offset, raw_len)`` per
-    span, None where the container is not kept. One histogram, one rank, one
-    encode and one plan launch for all spans, ONE sync (the per-span payload
-    totals), one assemble launch and one D2H of the dense containers, all on
-    the current stream. ``counts``, a contiguous ``len(spans) x 256`` int32
-    device tensor, is the spans' histograms at ``es`` where the caller has
-    them (``probe_spans_gpu``): the histogram launch is then left out."""
+    span, None where the container is not kept. One histogram, one rank and
+    one encode launch for all spans, then ``container.finish_containers`` (one
+    plan launch, ONE sync, one assemble launch, one D2H of the dense
+    containers), all on the current stream. ``counts``, a contiguous
+    ``len(spans) x 256`` int32 device tensor, is the spans' histograms at ``es``
+    where the caller has them (``probe_spans_gpu``): no histogram launch then."""
     import torch
-
-    from .staging import copy_from_device
 
     if es not in ELEM_SIZES:
         raise ValueError(f"element size {es} is not 2 or 4")
-    out: list = [None] * len(spans)
     if not spans:
-        return out
+        return []
     stream = torch.cuda.current_stream().cuda_stream
     n_segs = np.array([-(-ln // SEG_SIZE) for _off, ln in spans], dtype=np.int64)
     ends_seg = np.cumsum(n_segs)
     if int(ends_seg[-1]) > ws.n_seg:
         raise RuntimeError("compress spans exceed the workspace")
-    raw_lens = np.array([ln for _off, ln in spans], dtype=np.int64)
-    first_d = _to_dev((ends_seg - n_segs).astype(np.int32))
-    raw_d = _to_dev(raw_lens)
-    src_off_d = _to_dev(np.array([off for off, _ln in spans], dtype=np.int64))
+    first_d, raw_d, src_off_d = container.span_tables(spans, ends_seg - n_segs)
     tables = torch.empty(2, len(spans) * 256, dtype=torch.uint8, device="cuda")
     order_d, rank_d = tables[0], tables[1]
-    payload_d = torch.empty(len(spans), dtype=torch.int64, device="cuda")
     if counts is None:
         counts = torch.zeros(len(spans) * 256, dtype=torch.int32, device="cuda")
         rc = lib.ma_fpz_rank(
@@ -431,8 +404,8 @@ def compress_spans_gpu(
         rc = lib.ma_fpz_rank_counts(
             counts.data_ptr(), order_d.data_ptr(), rank_d.data_ptr(), len(spans), stream
         )
-    _check(rc, "fpz histogram/rank kernels")
-    _check(
+    container.check(rc, "fpz histogram/rank kernels")
+    container.check(
         lib.ma_fpz_encode(
             base, src_off_d.data_ptr(), raw_d.data_ptr(), first_d.data_ptr(),
             rank_d.data_ptr(), es, ws.stride.data_ptr(), OUT_STRIDE,
@@ -440,37 +413,19 @@ def compress_spans_gpu(
         ),
         "fpz encode kernel",
     )
-    _check(
-        lib.ma_malz_plan(
-            ws.comp_lens.data_ptr(), first_d.data_ptr(), raw_d.data_ptr(),
-            ws.seg_off.data_ptr(), payload_d.data_ptr(), len(spans), stream,
-        ),
-        "malz plan kernel",
-    )
-    totals = payload_d.cpu().numpy()  # the one sync
-    keep = worth_keeping(totals, raw_lens)
-    sizes = np.where(keep, HEADER_FIXED + 4 * n_segs + totals, 0)
-    ends = np.cumsum(sizes)
-    out_off = np.where(keep, ends - sizes, -1)  # -1: the kernel skips the span
-    dense_len = int(ends[-1])
-    if dense_len == 0:
-        return out
-    if dense_len > ws.dense.numel():
-        raise RuntimeError("dense containers exceed the workspace")
-    out_off_d = _to_dev(out_off)
-    _check(
-        lib.ma_fpz_assemble(
+
+    def assemble(out_off_d: Any) -> None:
+        rc = lib.ma_fpz_assemble(
             base, src_off_d.data_ptr(), ws.stride.data_ptr(), OUT_STRIDE,
             ws.comp_lens.data_ptr(), ws.seg_off.data_ptr(), first_d.data_ptr(),
             raw_d.data_ptr(), order_d.data_ptr(), es, ws.dense.data_ptr(),
             out_off_d.data_ptr(), len(spans), stream,
-        ),
-        "fpz assemble kernel",
+        )
+        container.check(rc, "fpz assemble kernel")
+
+    return container.finish_containers(
+        lib, spans, ws, first_d, raw_d, n_segs, HEADER_FIXED, assemble
     )
-    dense = copy_from_device(ws.dense.data_ptr(), dense_len)
-    for j in np.flatnonzero(keep):
-        out[j] = dense[out_off[j] : out_off[j] + sizes[j]]
-    return out
 
 
 def decompress_run_gpu(lib: Any, comp: int, headers: Sequence[Header], dst: int) -> int:
@@ -479,48 +434,30 @@ def decompress_run_gpu(lib: Any, comp: int, headers: Sequence[Header], dst: int)
     at device pointer ``comp`` and whose raw bytes are consecutive at ``dst``,
     on the current stream. Returns 0, or 1 + the run's first segment found
     corrupt; the stream has drained either way."""
-    import torch
-
     seg_lens = np.concatenate([np.asarray(h.seg_lens, dtype=np.int32) for h in headers])
     if len(seg_lens) == 0:
         return 0
     eff = np.concatenate([effective_lens(h.seg_lens, h.raw_len) for h in headers])
-    raw = np.concatenate([_seg_raw(len(h.seg_lens), h.raw_len) for h in headers])
+    raw = np.concatenate([seg_raw_lens(len(h.seg_lens), h.raw_len) for h in headers])
     comp_offs = np.cumsum(eff) - eff
     dst_offs = np.cumsum(raw) - raw
     blk = np.repeat(np.arange(len(headers), dtype=np.int32), [len(h.seg_lens) for h in headers])
-    offs_d = _to_dev(np.stack([comp_offs, dst_offs]).astype(np.int64))
-    ints_d = _to_dev(np.stack([seg_lens, raw.astype(np.int32), blk]).astype(np.int32))
-    order_d = _to_dev(np.concatenate([np.asarray(h.order, dtype=np.uint8) for h in headers]))
-    es_d = _to_dev(np.array([h.es for h in headers], dtype=np.uint8))
-    status = torch.full((1,), _STATUS_CLEAN, dtype=torch.int32, device="cuda")
-    n = len(seg_lens)
-    _check(
-        lib.ma_fpz_decode(
+    offs_d = container.to_dev(np.stack([comp_offs, dst_offs]).astype(np.int64))
+    ints_d = container.to_dev(np.stack([seg_lens, raw.astype(np.int32), blk]).astype(np.int32))
+    order_d = container.to_dev(np.concatenate([np.asarray(h.order, dtype=np.uint8) for h in headers]))
+    es_d = container.to_dev(np.array([h.es for h in headers], dtype=np.uint8))
+    return container.decode_status(
+        lambda status, stream: lib.ma_fpz_decode(
             comp, offs_d[0].data_ptr(), offs_d[1].data_ptr(), ints_d[0].data_ptr(),
             ints_d[1].data_ptr(), ints_d[2].data_ptr(), order_d.data_ptr(),
-            es_d.data_ptr(), dst, status.data_ptr(), n,
-            torch.cuda.current_stream().cuda_stream,
+            es_d.data_ptr(), dst, status, len(seg_lens), stream,
         ),
         "fpz decode kernel",
     )
-    first_bad = int(status.item())  # syncs: the tables may be freed
-    return 0 if first_bad == _STATUS_CLEAN else first_bad
 
 
 def decompress_buffer_gpu(blob: bytes) -> bytes:
-    hdr = validate_container(blob)  # before any launch
-    lib = load_lib(required=True)
-    import torch
-
-    from .staging import fetch_from_gpu, stage_to_gpu
-
-    comp = stage_to_gpu(memoryview(blob)[hdr.payload_off :])
-    dst = torch.empty(hdr.raw_len, dtype=torch.uint8, device="cuda")
-    bad = decompress_run_gpu(lib, comp.data_ptr(), [hdr], dst.data_ptr())
-    if bad:
-        raise ValueError(corrupt_message(bad))
-    return fetch_from_gpu(dst)
+    return container.decompress_buffer_gpu(sys.modules[__name__], blob)
 
 
 # ---------------------------------------------------------------------------
@@ -535,7 +472,7 @@ def compress_buffer_gpu(data: bytes, es: int) -> Optional[bytes]:
     from .staging import stage_to_gpu
 
     src = stage_to_gpu(data)
-    ws = workspace_for([len(data)])
+    ws = Workspace.for_lengths([len(data)], HEADER_FIXED)
     return compress_spans_gpu(lib, src.data_ptr(), [(0, len(data))], es, ws)[0]
 
 

@@ -123,6 +123,7 @@ def test_malformed_container_raises_before_any_launch(monkeypatch):
         raise AssertionError("the ops library was loaded for a malformed container")
 
     monkeypatch.setattr("modal_amd.ops.compress.load_lib", no_launch)
+    monkeypatch.setattr("modal_amd.ops.container.load_lib", no_launch)  # where the decode body is
     for name, bad in mutations.items():
         with pytest.raises(ValueError):
             C.decompress_buffer_gpu(bad)

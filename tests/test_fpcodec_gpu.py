@@ -71,7 +71,7 @@ def test_encoder_matches_the_model_byte_for_byte(model, es):
     _devcodec, fpcodec, lib = _feature()
     names = _names(es)
     buf, spans = _upload([fc.corpus()[n][0] for n in names], es)
-    ws = fpcodec.workspace_for([ln for _off, ln in spans])
+    ws = fpcodec.Workspace.for_lengths([ln for _off, ln in spans], fpcodec.HEADER_FIXED)
     got = fpcodec.compress_spans_gpu(lib, buf.data_ptr(), spans, es, ws)
     assert any(model[n] is None for n in names) and any(model[n] is not None for n in names)
     for name, z in zip(names, got):
@@ -86,7 +86,7 @@ def test_hand_assembled_container_from_the_kernels():
     from modal_amd.ops import compress
 
     buf, spans = _upload([fc.HAND_RAW], 2)
-    ws = fpcodec.workspace_for([128])
+    ws = fpcodec.Workspace.for_lengths([128], fpcodec.HEADER_FIXED)
     got = fpcodec.compress_spans_gpu(lib, buf.data_ptr(), spans, 2, ws)
     assert bytes(got[0]) == fc.HAND_CONTAINER
     assert compress.decompress_buffer_gpu(fc.HAND_CONTAINER) == fc.HAND_RAW

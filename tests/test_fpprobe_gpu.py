@@ -136,7 +136,7 @@ def test_encoder_on_the_probes_tables_matches_the_model(es):
     buf, spans = _upload([fc.corpus()[n][0] for n in names], es)
     _found, tables = fpcodec.probe_spans_gpu(lib, buf.data_ptr(), spans)
     assert tables.shape == (len(spans), 2, 256)
-    ws = fpcodec.workspace_for([ln for _off, ln in spans])
+    ws = fpcodec.Workspace.for_lengths([ln for _off, ln in spans], fpcodec.HEADER_FIXED)
     got = fpcodec.compress_spans_gpu(
         lib, buf.data_ptr(), spans, es, ws, counts=tables[:, es // 2 - 1].contiguous()
     )
