@@ -87,6 +87,18 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
             )
             lib.ma_fpz_decode.restype = ctypes.c_int
             lib.ma_fpz_decode.argtypes = [ptr] * 10 + [i32, ptr]
+            lib.ma_bytez_rank.restype = ctypes.c_int
+            lib.ma_bytez_rank.argtypes = [ptr] * 6 + [i32, ptr]
+            lib.ma_bytez_encode.restype = ctypes.c_int
+            lib.ma_bytez_encode.argtypes = (
+                [ptr] * 6 + [i32, ptr, i32, ctypes.c_long, ptr]
+            )
+            lib.ma_bytez_assemble.restype = ctypes.c_int
+            lib.ma_bytez_assemble.argtypes = (
+                [ptr] * 3 + [i32] + [ptr] * 7 + [i32, ptr]
+            )
+            lib.ma_bytez_decode.restype = ctypes.c_int
+            lib.ma_bytez_decode.argtypes = [ptr] * 9 + [i32, ptr]
             from .rawmem import _bind as _bind_rawmem
 
             _bind_rawmem(lib)

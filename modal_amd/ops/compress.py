@@ -14,7 +14,8 @@ What only MALZ41 knows lives here once: its header (``validate_container``,
 the only parser), the LZ4 launches in front of the shared encoder tail
 (``compress_spans_gpu``, the only device encoder) and the LZ4 decode launch
 (``decompress_run_gpu``). The segmented container under it is
-ops/container.py, which MAFP10 (ops/fpcodec.py) stands on as well.
+ops/container.py, which MAFP10 (ops/fpcodec.py) and MAFB10 (ops/bytecodec.py)
+stand on as well.
 
 ``compress_buffer_gpu``/``compress_buffers_gpu`` (blobs) and ops/devcodec.py
 (snapshots) are thin callers of these, so their containers are byte-identical
@@ -78,11 +79,14 @@ def is_compressed(blob: bytes) -> bool:
 
 def codec_of(blob: bytes) -> Any:
     """The module that reads a stored container: fpcodec for the MAFP10 magic,
-    this one otherwise. Whether a blob is compressed at all is out of band (the
-    ``.z`` suffix), so the magic only has to tell our two formats apart."""
-    from . import compress, fpcodec  # here, so that importing this module needs no numpy
+    bytecodec for MAFB10, this one otherwise. Whether a blob is compressed at
+    all is out of band (the ``.z`` suffix), so the magic only has to tell our
+    formats apart."""
+    from . import bytecodec, compress, fpcodec  # here, so that importing this module needs no numpy
 
-    return fpcodec if fpcodec.is_fp_container(blob) else compress
+    if fpcodec.is_fp_container(blob):
+        return fpcodec
+    return bytecodec if bytecodec.is_byte_container(blob) else compress
 
 
 # ---------------------------------------------------------------------------

@@ -1,8 +1,9 @@
-"""The segmented container under MALZ41 (ops/compress.py) and MAFP10
-(ops/fpcodec.py): a fixed header, a ``<u4`` table with one length per 4 KiB
-segment of the raw bytes (0: stored raw), the segments back to back. What
-follows from that alone lives here once and imports neither codec; a codec
-adds its magic, its own header fields and checks, and its kernels.
+"""The segmented container under MALZ41 (ops/compress.py), MAFP10
+(ops/fpcodec.py) and MAFB10 (ops/bytecodec.py): a fixed header, a ``<u4``
+table with one length per 4 KiB segment of the raw bytes (0: stored raw), the
+segments back to back. What follows from that alone lives here once and
+imports no codec; a codec adds its magic, its own header fields and checks,
+and its kernels.
 """
 
 from __future__ import annotations
@@ -156,6 +157,24 @@ def finish_containers(
     for j in np.flatnonzero(keep):
         out[j] = dense[out_off[j] : out_off[j] + sizes[j]]
     return out
+
+
+def run_tables(headers: Sequence) -> tuple:
+    """Per segment of a run of validated containers whose payloads lie back to
+    back and whose raw bytes are consecutive, on the device: (int64 rows: offset
+    in the payloads, offset in the raw bytes; int32 rows: seg_len, raw length,
+    index of its container; the order tables, 256 bytes per container; the
+    number of segments). For the codecs whose headers carry an order table."""
+    import numpy as np
+
+    seg_lens = np.concatenate([np.asarray(h.seg_lens, dtype=np.int32) for h in headers])
+    eff = np.concatenate([effective_lens(h.seg_lens, h.raw_len) for h in headers])
+    raw = np.concatenate([seg_raw_lens(len(h.seg_lens), h.raw_len) for h in headers])
+    blk = np.repeat(np.arange(len(headers), dtype=np.int32), [len(h.seg_lens) for h in headers])
+    offs_d = to_dev(np.stack([np.cumsum(eff) - eff, np.cumsum(raw) - raw]).astype(np.int64))
+    ints_d = to_dev(np.stack([seg_lens, raw.astype(np.int32), blk]).astype(np.int32))
+    order_d = to_dev(np.concatenate([np.asarray(h.order, dtype=np.uint8) for h in headers]))
+    return offs_d, ints_d, order_d, len(seg_lens)
 
 
 def decode_status(launch: Callable[[int, int], int], what: str) -> int:

@@ -1,0 +1,525 @@
+// MAFB10 byte-plane codec on the device for gfx950 (MI355X, CDNA4).
+//
+// The container (layout and rules in ops/bytecodec.py, whose numpy codec is
+// the model these kernels match byte for byte) is MAFP10's with 1-byte
+// elements: EVERY byte of a block is coded as its rank in the block's
+// frequency order, at a bit width chosen per 4 KiB segment, the rare ranks
+// escaped. It is for fp8 tensors, fp8 KV caches and e8m0 scale tensors.
+//
+//   hist      per block: LDS histogram of all its bytes, one global merge
+//   rank      fpz_rank_kernel (fpz.hip), through ma_fpz_rank_counts
+//   encode    one wavefront per segment -> its stride slot + comp_lens
+//   assemble  header + order + seg_len table + segments
+//   decode    one wavefront per segment of a run of containers
+//
+// Encode and decode run one wavefront per workgroup, so __syncthreads() is a
+// wave-level LDS fence and every branch around it is wave-uniform.
+//
+// Data path. fpz.hip reads strided top bytes out of a staged segment; here
+// there is no stride, so a segment is staged into LDS AT OFFSET 0 (aligned
+// dword loads, funnel-shifted by the source misalignment on the way in) and
+// a lane's run of lane_run(m) consecutive bytes, 64 of a full segment, is
+// whole dwords. The lane reads them once into registers, looks every byte's
+// rank up in the 256-byte LDS table and keeps raw bytes and ranks in
+// registers for both passes. Runs 16 dwords apart would fall on two banks, so
+// one pad dword follows every 16 (dword k of the segment is in32[k + k/16]).
+//
+// Escapes of all seven widths come from one value per element: rank r escapes
+// at width b exactly when floor(log2(r + 1)) >= b, so a lane counts
+// 31 - clz(r + 1) into nine 7-bit bins of one 64-bit register and the suffix
+// sums of the bins are its escapes at b = 7 .. 1.
+//
+// The code stream begins one byte into the segment (after the width byte),
+// so a lane's codes, whole bytes at a dword-multiple offset, sit one byte off
+// the slot's dwords. A lane therefore takes the last code byte of the lane
+// before it (lane 0: the width byte) in front of its own and stores aligned
+// dwords; the one byte left at the end is stored alone. Where the dword
+// stores do not apply (a partial last run, an unaligned slot) the code groups
+// pass through the staging buffer and go out a byte per lane.
+//
+// The decoder rebuilds a lane's 64 output bytes in registers and stores them
+// straight to global memory with 16-byte stores when the destination allows,
+// else through a linear LDS buffer and lds_to_global: dword writes, no
+// strided LDS byte writes.
+//
+// Measured on an MI355X (hipEvent times, median of 10 interleaved launches,
+// 64 MiB in 8 x 8 MiB spans: N(0,1) as float8_e4m3fn here, as bf16 for the
+// MAFP10 kernels of fpz.hip at es = 2 beside it; containers 0.8855 and 0.7127
+// of raw):
+//                  bytez (64 Mi elements)   fpz es 2 (32 Mi elements)
+//   hist + rank    29.5 us                  78.5 us
+//   encode         101.0 us                 67.2 us
+//   decode         87.8 us                  76.7 us
+// Encoder and decoder are slower per source byte than MAFP10's (1.50x, 1.15x)
+// and faster per element. LDS counters say it is not the LDS: fewer LDS
+// instructions than the fpz kernels, a tenth of the decoder's bank conflicts,
+// LDS busy under 2 % of the wave cycles; the per-element code extraction and
+// the stores are what is left. More in profiles/README.md, "Byte-plane codec".
+
+#include "malz_common.h"
+#include "rank_common.h"
+
+#define BZ_HEADER_FIXED 276  // magic 6, raw_len 8, es 1, reserved 1, n_seg 4, order 256
+#define BZ_HIST_BLOCK 256
+#define BZ_HIST_GROUPS 64
+#define BZ_HIST_COPIES 16
+#define BZ_HIST_UNROLL 4  // 16-byte loads a lane has in flight
+#define BZ_RUN_DWORDS 16  // a lane's run is at most 64 bytes
+// 4096 bytes, a pad dword per 16, and the two dwords an unaligned 8-byte read
+// of the last code bytes may touch behind them
+#define BZ_IN_DWORDS (SEG_SIZE / 4 + SEG_SIZE / 64 + 4)
+
+extern "C" int ma_fpz_rank_counts(const void* counts, void* order, void* rank_of, int n_blocks,
+                                  void* stream);
+
+__device__ __forceinline__ int padw(int k) { return k + (k >> 4); }           // dword k
+__device__ __forceinline__ int padb(int i) { return i + ((i >> 6) << 2); }    // byte i
+
+// len bytes at src -> LDS so that byte i of the segment is byte padb(i):
+// aligned dword loads, each lane's dword completed with the next lane's.
+// Every dword loaded holds at least one of the segment's own bytes.
+__device__ __forceinline__ void stage_at_zero(const uint8_t* __restrict__ src, int len,
+                                              uint32_t* in32, int lane) {
+  const int mis = (int)(reinterpret_cast<uintptr_t>(src) & 3);
+  const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src - mis);
+  const int n_src = (mis + len + 3) >> 2;
+  const int n_out = (len + 3) >> 2;
+  const int sh = 8 * mis;
+  for (int base = 0; base < n_out; base += WAVE) {  // wave-uniform: the shuffle needs all lanes
+    const int k = base + lane;
+    const uint32_t w0 = k < n_src ? s1[k] : 0u;
+    uint32_t w1 = __shfl_down(w0, 1, WAVE);
+    if (lane == WAVE - 1) w1 = (mis && k + 1 < n_src) ? s1[k + 1] : 0u;
+    if (k < n_out) in32[padw(k)] = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// histogram of every byte of a block
+// ---------------------------------------------------------------------------
+//
+// Loads as in fpz_probe_kernel: aligned 16-byte chunks from the chunk the
+// span's first byte lives in; only the first and the last chunk can hold
+// bytes outside the span and take the per-byte check. LDS as there too:
+// bins[bin][copy], copy = lane % 16, so the bank depends on the lane and
+// hardly on the data. fp8 Gaussians put a fifth of the bytes on four bins.
+
+__device__ __forceinline__ void bz_count(const uint4 v, int64_t q, int mis16, int64_t n,
+                                         uint32_t* mine) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  const int64_t i0 = 16 * q - mis16;  // span offset of the chunk's first byte
+  if (i0 >= 0 && i0 + 16 <= n) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        atomicAdd(mine + ((w[d] >> (8 * k)) & 255u) * BZ_HIST_COPIES, 1u);
+  } else {  // the span's first or last chunk: count only its own bytes
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int64_t i = i0 + 4 * d + k;
+        if (i >= 0 && i < n) atomicAdd(mine + ((w[d] >> (8 * k)) & 255u) * BZ_HIST_COPIES, 1u);
+      }
+  }
+}
+
+extern "C" __global__ __launch_bounds__(BZ_HIST_BLOCK) void bytez_hist_kernel(
+    const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_src_off,
+    const int64_t* __restrict__ blk_raw_len, uint32_t* __restrict__ counts, int blk_base) {
+  __shared__ uint32_t bins[256 * BZ_HIST_COPIES];
+  const int b = blk_base + blockIdx.y;
+  const int tid = threadIdx.x;
+  const int64_t n = blk_raw_len[b];
+  if (n <= 0) return;
+  const uint8_t* first = src + blk_src_off[b];
+  const int mis16 = (int)(reinterpret_cast<uintptr_t>(first) & 15);
+  const int64_t n_chunks = (mis16 + n + 15) >> 4;  // the last one holds byte n - 1
+  if ((int64_t)blockIdx.x * BZ_HIST_BLOCK >= n_chunks) return;  // nothing here: no merge either
+
+  uint4* z = reinterpret_cast<uint4*>(bins);
+  for (int k = tid; k < 256 * BZ_HIST_COPIES / 4; k += BZ_HIST_BLOCK) z[k] = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+
+  const uint4* chunks = reinterpret_cast<const uint4*>(first - mis16);
+  uint32_t* mine = &bins[tid & (BZ_HIST_COPIES - 1)];
+  const int64_t step = (int64_t)gridDim.x * BZ_HIST_BLOCK;
+  int64_t q = (int64_t)blockIdx.x * BZ_HIST_BLOCK + tid;
+  for (; q + (BZ_HIST_UNROLL - 1) * step < n_chunks; q += BZ_HIST_UNROLL * step) {
+    uint4 v[BZ_HIST_UNROLL];
+#pragma unroll
+    for (int u = 0; u < BZ_HIST_UNROLL; ++u) v[u] = chunks[q + u * step];
+#pragma unroll
+    for (int u = 0; u < BZ_HIST_UNROLL; ++u) bz_count(v[u], q + u * step, mis16, n, mine);
+  }
+  for (; q < n_chunks; q += step) bz_count(chunks[q], q, mis16, n, mine);
+  __syncthreads();
+  uint32_t total = 0;
+  for (int k = 0; k < BZ_HIST_COPIES; ++k)  // rotated by the thread: off one bank
+    total += bins[tid * BZ_HIST_COPIES + ((k + tid) & (BZ_HIST_COPIES - 1))];
+  if (total) atomicAdd(&counts[(int64_t)b * 256 + tid], total);
+}
+
+// ---------------------------------------------------------------------------
+// encode: one wavefront per segment
+// ---------------------------------------------------------------------------
+
+// Append nb (<= 4) bytes to a lane's pending output (acc holds nacc <= 3
+// bytes) and store the dword that completes.
+__device__ __forceinline__ void push_bytes(uint32_t x, int nb, uint64_t& acc, int& nacc,
+                                           uint32_t*& o32) {
+  acc |= (uint64_t)x << (8 * nacc);
+  nacc += nb;
+  if (nacc >= 4) {
+    *o32++ = (uint32_t)acc;
+    acc >>= 32;
+    nacc -= 4;
+  }
+}
+
+extern "C" __global__ __launch_bounds__(WAVE) void bytez_encode_kernel(
+    const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_src_off,
+    const int64_t* __restrict__ blk_raw_len, const int32_t* __restrict__ blk_first_seg,
+    const uint8_t* __restrict__ rank_tab, uint8_t* __restrict__ stride_buf, int out_stride,
+    int32_t* __restrict__ comp_lens, int blk_base) {
+  __shared__ __attribute__((aligned(16))) uint32_t in32[BZ_IN_DWORDS];
+  __shared__ uint32_t rank32[256 / 4];
+  const uint8_t* rank = reinterpret_cast<const uint8_t*>(rank32);
+  const int lane = threadIdx.x;
+  const int bk = blk_base + blockIdx.y;
+  const int64_t raw_len = blk_raw_len[bk];
+  const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
+  const int64_t first = blk_first_seg[bk];
+  const uint8_t* blk_src = src + blk_src_off[bk];
+  if ((int64_t)blockIdx.x >= n_seg) return;
+  rank32[lane] = reinterpret_cast<const uint32_t*>(rank_tab + (int64_t)bk * 256)[lane];
+
+  for (int64_t s = blockIdx.x; s < n_seg; s += gridDim.x) {
+    __syncthreads();  // the last segment's readers are done; rank is visible
+    const int m = seg_eff(0, raw_len, s);
+    int32_t* clen = comp_lens + first + s;
+    if (m < 3) {  // hi >= 2, so fewer than 3 elements never code
+      if (lane == 0) *clen = 0;
+      continue;
+    }
+    stage_at_zero(blk_src + s * SEG_SIZE, m, in32, lane);
+    __syncthreads();
+
+    const int per = lane_run(m);
+    const int ndw = per >> 2, ngrp = per >> 3;
+    const int i0 = lane * per;
+    // The lane's bytes and their ranks, four to a register. No branch per
+    // element: a run is read whole (the staging buffer covers 64 whole runs,
+    // what lies past m is stale), every byte is looked up, and the ranks past
+    // m are masked to 0. Rank 0 never escapes, codes as zero bits and counts
+    // into bin 0, which no width reads.
+    const int mine_n = min(max(m - i0, 0), per);  // the lane's elements
+    uint32_t raw[BZ_RUN_DWORDS], rk[BZ_RUN_DWORDS];
+    uint64_t bins = 0;  // nine 7-bit counts of floor(log2(rank + 1))
+#pragma unroll
+    for (int d = 0; d < BZ_RUN_DWORDS; ++d) {
+      raw[d] = 0;
+      rk[d] = 0;
+      if (d < ndw) {  // wave-uniform
+        const uint32_t w = in32[padw((i0 >> 2) + d)];
+        const int inside = min(max(mine_n - 4 * d, 0), 4);
+        uint32_t r4 = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r4 |= (uint32_t)rank[(w >> (8 * k)) & 255u] << (8 * k);
+        r4 &= (uint32_t)((1ull << (8 * inside)) - 1);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          bins += 1ull << (7 * (31 - __clz((int)(((r4 >> (8 * k)) & 255u) + 1))));
+        raw[d] = w;
+        rk[d] = r4;
+      }
+    }
+    // mine[b-1]: this lane's elements that width b would escape
+    int mine[7];
+    int suffix = (int)(bins >> 56) & 127;
+#pragma unroll
+    for (int w = 7; w >= 1; --w) {
+      suffix += (int)(bins >> (7 * w)) & 127;
+      mine[w - 1] = suffix;
+    }
+    // a segment has at most 4096 escapes: two widths share one wave_sum
+    int total[8];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int both = wave_sum(mine[2 * p] | (p < 3 ? mine[2 * p + 1] << 16 : 0));
+      total[2 * p] = both & 0xFFFF;
+      total[2 * p + 1] = both >> 16;
+    }
+    int b = 0, hi = m, my_esc = 0;  // a width must beat hi = m to be kept
+#pragma unroll
+    for (int w = 1; w <= 7; ++w) {
+      const int cost = 1 + ((m * w + 7) >> 3) + total[w - 1];
+      if (cost < hi) { hi = cost; b = w; my_esc = mine[w - 1]; }
+    }
+    if (b == 0) {
+      if (lane == 0) *clen = 0;
+      continue;
+    }
+
+    const uint32_t E = (1u << b) - 1;
+    const int nbytes = (m * b + 7) >> 3;
+    uint8_t* out = stride_buf + (first + s) * out_stride;
+    uint8_t* escs = out + 1 + nbytes + wave_excl_scan(my_esc, lane);
+    // v[g]: the b code bytes of the lane's g-th group of 8 elements
+    uint64_t v[BZ_RUN_DWORDS / 2];
+    uint32_t last = 0;  // the last code byte of the lane's run
+#pragma unroll
+    for (int g = 0; g < BZ_RUN_DWORDS / 2; ++g) {
+      v[g] = 0;
+      if (g < ngrp) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int d = 2 * g + (j >> 2), sh = 8 * (j & 3);
+          uint32_t r = (rk[d] >> sh) & 255u;
+          if (r >= E) { *escs++ = (uint8_t)(raw[d] >> sh); r = E; }
+          v[g] |= (uint64_t)r << (j * b);
+        }
+        if (g == ngrp - 1) last = (uint32_t)(v[g] >> (8 * (b - 1))) & 255u;
+      }
+    }
+    // Lanes whose whole run is inside the segment store dwords: the slot's
+    // dword at the lane's offset begins with the byte before its codes.
+    const int lb = ngrp * b;  // code bytes per lane
+    const int nfull = m / per;
+    const bool vec = (reinterpret_cast<uintptr_t>(out) & 3) == 0 && (lb & 3) == 0;
+    const uint32_t before = __shfl_up(last, 1, WAVE);
+    if (vec && lane < nfull) {
+      uint32_t* o32 = reinterpret_cast<uint32_t*>(out + lane * lb);
+      uint64_t acc = lane == 0 ? (uint32_t)b : before;
+      int nacc = 1;
+#pragma unroll
+      for (int g = 0; g < BZ_RUN_DWORDS / 2; ++g)
+        if (g < ngrp) {
+          push_bytes((uint32_t)v[g], b < 4 ? b : 4, acc, nacc, o32);
+          if (b > 4) push_bytes((uint32_t)(v[g] >> 32), b - 4, acc, nacc, o32);
+        }
+      if (lane == nfull - 1) out[nfull * lb] = (uint8_t)last;
+    }
+    // What the dword stores leave (all of the stream without them, a partial
+    // last run with them) goes out as bytes, a lane per byte: the groups pass
+    // through the staging buffer, which every lane has read by now.
+    if (!vec || m % per) {  // wave-uniform
+      __syncthreads();
+      uint64_t* groups = reinterpret_cast<uint64_t*>(in32);
+#pragma unroll
+      for (int g = 0; g < BZ_RUN_DWORDS / 2; ++g)
+        if (g < ngrp) groups[lane * ngrp + g] = v[g];
+      __syncthreads();
+      for (int t = (vec ? nfull * lb : 0) + lane; t < nbytes; t += WAVE) {
+        const int g = t / b;
+        out[1 + t] = (uint8_t)(groups[g] >> (8 * (t - g * b)));
+      }
+      if (lane == 0 && (!vec || nfull == 0)) out[0] = (uint8_t)b;
+    }
+    if (lane == 0) *clen = hi;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// assemble
+// ---------------------------------------------------------------------------
+
+extern "C" __global__ __launch_bounds__(ASM_BLOCK) void bytez_assemble_kernel(
+    const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_src_off,
+    const uint8_t* __restrict__ stride_buf, int out_stride,
+    const int32_t* __restrict__ comp_lens, const int64_t* __restrict__ seg_off,
+    const int32_t* __restrict__ blk_first_seg, const int64_t* __restrict__ blk_raw_len,
+    const uint8_t* __restrict__ order, uint8_t* __restrict__ out,
+    const int64_t* __restrict__ blk_out_off, int blk_base) {
+  const int b = blk_base + blockIdx.y;
+  const int64_t out_off = blk_out_off[b];
+  if (out_off < 0) return;  // container not kept: nothing to assemble
+  const int64_t raw_len = blk_raw_len[b];
+  const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
+  uint8_t* blk_out = out + out_off;
+
+  if (blockIdx.x == 0 && threadIdx.x < WAVE) {
+    const int lane = threadIdx.x;
+    const uint64_t magic = 0x30314246414DULL;  // "MAFB10", little-endian
+    put_le(blk_out, magic, 6, lane);
+    put_le(blk_out + 6, (uint64_t)raw_len, 8, lane);
+    put_le(blk_out + 14, 1, 2, lane);  // es 1, then the reserved 0
+    put_le(blk_out + 16, (uint64_t)n_seg, 4, lane);
+    wave_copy(order + (int64_t)b * 256, blk_out + 20, 256, lane);
+  }
+  assemble_segments(blk_out + BZ_HEADER_FIXED, src + blk_src_off[b], stride_buf, out_stride,
+                    comp_lens, seg_off, blk_first_seg[b], raw_len, n_seg);
+}
+
+// ---------------------------------------------------------------------------
+// decode: one wavefront per segment of a run of containers
+// ---------------------------------------------------------------------------
+
+// The 8 staged bytes from byte `at` on, as one word.
+__device__ __forceinline__ uint64_t lds_bytes8(const uint32_t* in32, int at) {
+  const int k = at >> 2, sh = 8 * (at & 3);
+  const uint32_t d0 = in32[padw(k)], d1 = in32[padw(k + 1)], d2 = in32[padw(k + 2)];
+  const uint32_t lo = (uint32_t)((((uint64_t)d1 << 32) | d0) >> sh);
+  const uint32_t hi = (uint32_t)((((uint64_t)d2 << 32) | d1) >> sh);
+  return ((uint64_t)hi << 32) | lo;
+}
+
+// *status comes in as INT32_MAX and leaves as the min of seg + 1 over the
+// segments that are malformed (untouched: none). A malformed segment writes
+// nothing; no segment reads outside its seg_len bytes (rounded out to aligned
+// dwords) or writes outside its raw bytes.
+extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
+    const uint8_t* __restrict__ comp, const int64_t* __restrict__ comp_offs,
+    const int64_t* __restrict__ dst_offs, const int32_t* __restrict__ seg_lens,
+    const int32_t* __restrict__ seg_raw, const int32_t* __restrict__ seg_blk,
+    const uint8_t* __restrict__ orders, uint8_t* __restrict__ dst,
+    int32_t* __restrict__ status, int n_segments) {
+  __shared__ uint32_t in32[BZ_IN_DWORDS];
+  __shared__ uint32_t out32[SEG_SIZE / 4];
+  __shared__ uint32_t order32[256 / 4];
+  const uint8_t* in = reinterpret_cast<const uint8_t*>(in32);
+  const uint8_t* order = reinterpret_cast<const uint8_t*>(order32);
+  const int lane = threadIdx.x;
+
+  for (int seg = blockIdx.x; seg < n_segments; seg += gridDim.x) {
+    __syncthreads();  // the last segment's LDS readers are done
+    const uint8_t* sp = comp + comp_offs[seg];
+    uint8_t* d = dst + dst_offs[seg];
+    const int m = seg_raw[seg];
+    const int slen = seg_lens[seg];
+    bool ok = m > 0 && m <= SEG_SIZE;
+    if (ok && slen == 0) {  // stored raw
+      wave_copy(sp, d, m, lane);
+      continue;
+    }
+    ok = ok && slen >= 2 && slen < m;
+    int b = 0, nbytes = 0;
+    if (ok) {
+      order32[lane] = reinterpret_cast<const uint32_t*>(orders + (int64_t)seg_blk[seg] * 256)[lane];
+      stage_at_zero(sp, slen, in32, lane);
+    }
+    __syncthreads();
+    if (ok) {
+      b = in[0];
+      nbytes = (m * b + 7) >> 3;
+      ok = b >= 1 && b <= 7 && 1 + nbytes <= slen;
+    }
+    if (!ok) b = 0;
+    const int per = lane_run(m);
+    const int ndw = per >> 2, ngrp = per >> 3;
+    const int i0 = lane * per;
+    const uint32_t E = (1u << b) - 1;
+    uint64_t v[BZ_RUN_DWORDS / 2];  // the lane's codes, 8 elements a word
+    int my_esc = 0;
+#pragma unroll
+    for (int g = 0; g < BZ_RUN_DWORDS / 2; ++g) {
+      v[g] = 0;
+      if (ok && g < ngrp && i0 + 8 * g < m) {
+        v[g] = lds_bytes8(in32, 1 + ((i0 >> 3) + g) * b);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          my_esc += (i0 + 8 * g + j < m) && (uint32_t)((v[g] >> (j * b)) & E) == E;
+      }
+    }
+    // the escapes must be exactly what is left of seg_len
+    ok = ok && wave_sum(my_esc) == slen - 1 - nbytes;
+    if (!ok) {
+      if (lane == 0) atomicMin(status, seg + 1);  // the FIRST malformed one
+      continue;
+    }
+    int esc_at = 1 + nbytes + wave_excl_scan(my_esc, lane);
+    uint32_t o[BZ_RUN_DWORDS];
+#pragma unroll
+    for (int q = 0; q < BZ_RUN_DWORDS; ++q) {
+      o[q] = 0;
+      if (q < ndw) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (i0 + 4 * q + k < m) {
+            const uint32_t code = (uint32_t)(v[q >> 1] >> ((4 * (q & 1) + k) * b)) & E;
+            const uint32_t byte = code == E ? in[padb(esc_at++)] : order[code];
+            o[q] |= byte << (8 * k);
+          }
+      }
+    }
+    // whole runs to a 16-byte aligned destination: straight from registers
+    const bool direct = (reinterpret_cast<uintptr_t>(d) & 15) == 0 && (per & 15) == 0 && m % per == 0;
+    if (direct) {
+      uint4* d4 = reinterpret_cast<uint4*>(d + i0);
+#pragma unroll
+      for (int q = 0; q < BZ_RUN_DWORDS / 4; ++q)
+        if (4 * q < ndw && i0 < m) d4[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < BZ_RUN_DWORDS; ++q)
+        if (q < ndw && i0 + 4 * q < m) out32[(i0 >> 2) + q] = o[q];
+      __syncthreads();
+      lds_to_global(reinterpret_cast<const uint8_t*>(out32), d, m, lane);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host entry points
+// ---------------------------------------------------------------------------
+
+// counts (n_blocks x 256 u32) must come in zeroed.
+extern "C" int ma_bytez_rank(const void* src, const void* blk_src_off, const void* blk_raw_len,
+                             void* counts, void* order, void* rank_of, int n_blocks,
+                             void* stream) {
+  if (n_blocks <= 0) return 0;
+  const int rc = launch_chunked(n_blocks, [&](int base, int ny) {
+    hipLaunchKernelGGL(bytez_hist_kernel, dim3(BZ_HIST_GROUPS, ny), dim3(BZ_HIST_BLOCK), 0,
+                       (hipStream_t)stream, (const uint8_t*)src,
+                       (const int64_t*)blk_src_off, (const int64_t*)blk_raw_len,
+                       (uint32_t*)counts, base);
+  });
+  return rc ? rc : ma_fpz_rank_counts(counts, order, rank_of, n_blocks, stream);
+}
+
+// max_segs: the largest segment count of any block (bounds the grid).
+extern "C" int ma_bytez_encode(const void* src, const void* blk_src_off,
+                               const void* blk_raw_len, const void* blk_first_seg,
+                               const void* rank_of, void* stride_buf, int out_stride,
+                               void* comp_lens, int n_blocks, long max_segs, void* stream) {
+  if (n_blocks <= 0 || max_segs <= 0) return 0;
+  const int gx = (int)(max_segs < 16384 ? max_segs : 16384);
+  return launch_chunked(n_blocks, [&](int base, int ny) {
+    hipLaunchKernelGGL(bytez_encode_kernel, dim3(gx, ny), dim3(WAVE), 0, (hipStream_t)stream,
+                       (const uint8_t*)src, (const int64_t*)blk_src_off,
+                       (const int64_t*)blk_raw_len, (const int32_t*)blk_first_seg,
+                       (const uint8_t*)rank_of, (uint8_t*)stride_buf, out_stride,
+                       (int32_t*)comp_lens, base);
+  });
+}
+
+extern "C" int ma_bytez_assemble(const void* src, const void* blk_src_off,
+                                 const void* stride_buf, int out_stride,
+                                 const void* comp_lens, const void* seg_off,
+                                 const void* blk_first_seg, const void* blk_raw_len,
+                                 const void* order, void* out, const void* blk_out_off,
+                                 int n_blocks, void* stream) {
+  return launch_chunked(n_blocks, [&](int base, int ny) {
+    hipLaunchKernelGGL(bytez_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
+                       (hipStream_t)stream, (const uint8_t*)src,
+                       (const int64_t*)blk_src_off, (const uint8_t*)stride_buf, out_stride,
+                       (const int32_t*)comp_lens, (const int64_t*)seg_off,
+                       (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
+                       (const uint8_t*)order, (uint8_t*)out, (const int64_t*)blk_out_off, base);
+  });
+}
+
+extern "C" int ma_bytez_decode(const void* comp, const void* comp_offs, const void* dst_offs,
+                               const void* seg_lens, const void* seg_raw, const void* seg_blk,
+                               const void* orders, void* dst, void* status, int n_segments,
+                               void* stream) {
+  if (n_segments <= 0) return 0;
+  const int gx = n_segments < (1 << 20) ? n_segments : (1 << 20);
+  hipLaunchKernelGGL(bytez_decode_kernel, dim3(gx), dim3(WAVE), 0, (hipStream_t)stream,
+                     (const uint8_t*)comp, (const int64_t*)comp_offs,
+                     (const int64_t*)dst_offs, (const int32_t*)seg_lens,
+                     (const int32_t*)seg_raw, (const int32_t*)seg_blk,
+                     (const uint8_t*)orders, (uint8_t*)dst, (int32_t*)status, n_segments);
+  return (int)hipGetLastError();
+}

@@ -30,6 +30,7 @@
 // the global traffic and is left alone.
 
 #include "malz_common.h"
+#include "rank_common.h"
 
 #define FPZ_HEADER_FIXED 276  // magic 6, raw_len 8, es 1, reserved 1, n_seg 4, order 256
 #define HIST_BLOCK 256
@@ -40,10 +41,6 @@
 
 __device__ __forceinline__ int pad(int x) { return x + ((x >> 6) << 2); }
 
-// Elements per lane: ceil(m/64) rounded up to a multiple of 8, so a lane's
-// codes are whole bytes at every width. 32 for m = 2048, 16 for m = 1024.
-__device__ __forceinline__ int lane_run(int m) { return (((m + 63) >> 6) + 7) & ~7; }
-
 // len bytes at src -> LDS, padded; byte i of the segment is in[pad(mis + i)].
 // Every dword loaded holds at least one of the segment's own bytes.
 __device__ __forceinline__ int stage_in(const uint8_t* __restrict__ src, int len,
@@ -53,22 +50,6 @@ __device__ __forceinline__ int stage_in(const uint8_t* __restrict__ src, int len
   const int n_dw = (mis + len + 3) >> 2;
   for (int k = lane; k < n_dw; k += WAVE) in32[k + (k >> 4)] = s1[k];
   return mis;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, WAVE);
-  return v;
-}
-
-__device__ __forceinline__ int wave_excl_scan(int v, int lane) {
-  int incl = v;
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) {
-    int up = __shfl_up(incl, d, WAVE);
-    if (lane >= d) incl += up;
-  }
-  return incl - v;
 }
 
 // ---------------------------------------------------------------------------
@@ -370,25 +351,6 @@ extern "C" __global__ __launch_bounds__(ASM_BLOCK) void fpz_assemble_kernel(
 // ---------------------------------------------------------------------------
 // decode: one wavefront per segment of a run of containers
 // ---------------------------------------------------------------------------
-
-// len bytes of LDS -> dst at any alignment: byte lanes up to dst's 16-byte
-// boundary, dwordx4 stores on the body, byte lanes on the tail.
-__device__ __forceinline__ void lds_to_global(const uint8_t* from, uint8_t* __restrict__ dst, int len,
-                              int lane) {
-  int head = (int)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15);
-  if (head > len) head = len;
-  if (lane < head) dst[lane] = from[lane];
-  from += head; dst += head; len -= head;
-  const int n_vec = len >> 4;
-  uint4* d4 = reinterpret_cast<uint4*>(dst);
-  for (int k = lane; k < n_vec; k += WAVE) {
-    uint4 v;
-    __builtin_memcpy(&v, from + 16 * k, 16);
-    d4[k] = v;
-  }
-  const int tail_start = n_vec << 4;
-  if (lane < len - tail_start) dst[tail_start + lane] = from[tail_start + lane];
-}
 
 // The code bytes [cb, cb + b) of a lane's group of 8 elements as one word;
 // bytes at or past nbytes (the stream's end) read as zero.

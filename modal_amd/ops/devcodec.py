@@ -12,11 +12,14 @@ straight into the destination allocation, with ``validate_container`` and
 ``decompress_run_gpu`` of the codec the magic selects (``compress.codec_of``).
 
 An object the caller hints as float data (``elem_size`` 2 or 4) offers the
-blocks LZ4 declined to the float-plane codec (ops/fpcodec.py, MAFP10); an
-object of no known element type (``fpcodec.AUTO``) has those blocks probed on
-the device for the element size at which the codec pays, if any. Both
-codecs stand on ops/container.py and both validators return headers that
-begin (raw_len, seg lens, payload offset): nothing here tells them apart.
+blocks LZ4 declined to the float-plane codec (ops/fpcodec.py, MAFP10), one
+hinted as 1-byte elements (``elem_size`` 1: fp8, e8m0 scales) to the
+byte-plane codec (ops/bytecodec.py, MAFB10); an object of no known element
+type (``fpcodec.AUTO``) has those blocks probed on the device for the element
+size, 2 or 4, at which the float-plane codec pays, if any (the probe does not
+look for element size 1 yet). The codecs stand on ops/container.py and their
+validators return headers that begin (raw_len, seg lens, payload offset):
+nothing here tells them apart.
 
 What this module adds to those is the block layer: digests, skipping blocks
 the CAS already has, the cached 64 MiB scratch with its out-of-memory
@@ -37,15 +40,19 @@ from typing import Any, Callable, Iterator, NamedTuple, Optional, Sequence
 import numpy as np
 
 from ..scheduler.blobs import BLOCK_SIZE, BlobStore
-from . import compress, fpcodec, load_lib
+from . import bytecodec, compress, fpcodec, load_lib
 from .container import SEG_SIZE, Workspace
 from .hashing import GPU_MIN_BYTES, content_digest, leaf_table, sha256_leaves_gpu, tree_roots
 from .staging import copy_from_device, copy_to_device
 
 WINDOW = 64 * 1024 * 1024  # source bytes encoded per plan/assemble round
 COMPRESS_MIN = BlobStore.COMPRESS_MIN
+# Blocks hinted as 1-byte elements go to the byte-plane codec from this size:
+# the e8m0 scale tensor of an MX-quantised weight is 1/32 of it and rarely
+# reaches COMPRESS_MIN, and it is what the codec shrinks most.
+BYTE_MIN = 64 * 1024
 RUN_MAX_BLOCKS = 128  # decode: blocks per decompress launch, at most
-_ELEM_SIZES = (0, *fpcodec.ELEM_SIZES, fpcodec.AUTO)  # what an element size hint may be
+_ELEM_SIZES = (0, 1, *fpcodec.ELEM_SIZES, fpcodec.AUTO)  # what an element size hint may be
 _TREE_GROUP = 8  # verify: full blocks whose leaves share one hash dispatch
 
 
@@ -171,9 +178,11 @@ def _encode_window(
     ``digests`` holds the short blocks' digests; full blocks are None. With
     ``elem_size`` 2 or 4 the blocks LZ4 declined go through the float-plane
     codec on the same scratch (LZ4 first: a zero-filled float tensor is 0.4 %
-    under LZ4 and 56 % under MAFP10). With ``fpcodec.AUTO`` they are probed
-    first and each goes through it at the element size the probe found, or
-    stays raw where it found none."""
+    under LZ4 and 56 % under MAFP10), with ``elem_size`` 1 through the
+    byte-plane codec, which also takes the blocks of BYTE_MIN bytes and more
+    that are too short for LZ4. With ``fpcodec.AUTO`` they are probed first and each goes
+    through the float-plane codec at the element size the probe found (2 or
+    4), or stays raw where it found none."""
     tree = [i for i, d in enumerate(digests) if d is None]
     for i, d in zip(tree, _tree_digests(lib, ptr, [spans[i] for i in tree])):
         digests[i] = d
@@ -183,6 +192,10 @@ def _encode_window(
         zip(cand, compress.compress_spans_gpu(lib, ptr, [spans[i] for i in cand], sc))
     )
     left = [i for i in cand if containers[i] is None] if elem_size else []
+    if elem_size == 1:
+        left += [
+            i for i, (_o, ln) in enumerate(spans) if BYTE_MIN <= ln < COMPRESS_MIN and not skip[i]
+        ]
     if elem_size == fpcodec.AUTO and left:
         # one probe of all of them, then one encode per element size it
         # found, each on its rows of the probe's tables
@@ -197,6 +210,10 @@ def _encode_window(
                     counts=mine[:, col].contiguous(),
                 )
                 containers.update(zip([left[k] for k in rows], z))
+    elif left and elem_size == 1:
+        containers.update(
+            zip(left, bytecodec.compress_spans_gpu(lib, ptr, [spans[i] for i in left], sc))
+        )
     elif left:
         containers.update(
             zip(left, fpcodec.compress_spans_gpu(lib, ptr, [spans[i] for i in left], elem_size, sc))
@@ -226,14 +243,15 @@ def iter_encode_device(
     caller already has the block: it is yielded with ``payload=None`` and is
     neither compressed nor copied. ``elem_sizes`` has one entry per object:
     2 or 4 offers the blocks LZ4 declined to the float-plane codec
-    (ops/fpcodec.py), ``fpcodec.AUTO`` offers them at the element size a
-    probe of their bytes finds (per block; none: raw), 0 does not; digests
-    are of the RAW block either way."""
+    (ops/fpcodec.py), 1 to the byte-plane codec (ops/bytecodec.py),
+    ``fpcodec.AUTO`` offers them to the float-plane codec at the element size,
+    2 or 4, a probe of their bytes finds (per block; none: raw), 0 does not;
+    digests are of the RAW block either way."""
     _check_block_size(block_size)
     if elem_sizes is None:
         elem_sizes = [0] * len(objects)
     if len(elem_sizes) != len(objects) or any(es not in _ELEM_SIZES for es in elem_sizes):
-        raise ValueError("elem_sizes needs one of 0, 2, 4, fpcodec.AUTO per object")
+        raise ValueError("elem_sizes needs one of 0, 1, 2, 4, fpcodec.AUTO per object")
     lib = load_lib(required=True)
     all_spans = [_spans(nbytes, block_size) for _ptr, nbytes in objects]
     with _codec_lock:
@@ -378,10 +396,11 @@ def encode_host(
     data: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0
 ) -> list[EncodedBlock]:
     """Same manifest from host bytes (CPU tensors, CPU-only processes).
-    ``fpcodec.AUTO`` runs the probe's numpy twin on every block LZ4 declined."""
+    ``fpcodec.AUTO`` runs the probe's numpy twin, which knows element sizes
+    2 and 4, on every block LZ4 declined."""
     _check_block_size(block_size)
     if elem_size not in _ELEM_SIZES:
-        raise ValueError("elem_size is one of 0, 2, 4, fpcodec.AUTO")
+        raise ValueError("elem_size is one of 0, 1, 2, 4, fpcodec.AUTO")
     from .compress import compress_buffer
 
     view = memoryview(data).cast("B")
@@ -392,7 +411,9 @@ def encode_host(
         es = elem_size
         if z is None and es == fpcodec.AUTO and ln >= COMPRESS_MIN:
             es = fpcodec.choose_elem_size(*fpcodec.probe_counts_cpu(block), ln)[0]
-        if z is None and es and ln >= COMPRESS_MIN:
+        if z is None and es == 1 and ln >= BYTE_MIN:
+            z = bytecodec.compress_buffer(block)
+        elif z is None and es and ln >= COMPRESS_MIN:
             z = fpcodec.compress_buffer(block, es)
         if z is not None:
             blocks.append(EncodedBlock(content_digest(block), ln, z, True))

@@ -434,23 +434,15 @@ def decompress_run_gpu(lib: Any, comp: int, headers: Sequence[Header], dst: int)
     at device pointer ``comp`` and whose raw bytes are consecutive at ``dst``,
     on the current stream. Returns 0, or 1 + the run's first segment found
     corrupt; the stream has drained either way."""
-    seg_lens = np.concatenate([np.asarray(h.seg_lens, dtype=np.int32) for h in headers])
-    if len(seg_lens) == 0:
+    if not sum(len(h.seg_lens) for h in headers):
         return 0
-    eff = np.concatenate([effective_lens(h.seg_lens, h.raw_len) for h in headers])
-    raw = np.concatenate([seg_raw_lens(len(h.seg_lens), h.raw_len) for h in headers])
-    comp_offs = np.cumsum(eff) - eff
-    dst_offs = np.cumsum(raw) - raw
-    blk = np.repeat(np.arange(len(headers), dtype=np.int32), [len(h.seg_lens) for h in headers])
-    offs_d = container.to_dev(np.stack([comp_offs, dst_offs]).astype(np.int64))
-    ints_d = container.to_dev(np.stack([seg_lens, raw.astype(np.int32), blk]).astype(np.int32))
-    order_d = container.to_dev(np.concatenate([np.asarray(h.order, dtype=np.uint8) for h in headers]))
+    offs_d, ints_d, order_d, n_segments = container.run_tables(headers)
     es_d = container.to_dev(np.array([h.es for h in headers], dtype=np.uint8))
     return container.decode_status(
         lambda status, stream: lib.ma_fpz_decode(
             comp, offs_d[0].data_ptr(), offs_d[1].data_ptr(), ints_d[0].data_ptr(),
             ints_d[1].data_ptr(), ints_d[2].data_ptr(), order_d.data_ptr(),
-            es_d.data_ptr(), dst, status, len(seg_lens), stream,
+            es_d.data_ptr(), dst, status, n_segments, stream,
         ),
         "fpz decode kernel",
     )

@@ -318,11 +318,14 @@ def capture_manifest(store: Any, float_codec: Any = False) -> bytes:
     copied, so a second snapshot of unchanged state costs its hashing.
 
     ``float_codec`` True offers the blocks of registered bf16/fp16/fp32
-    tensors that LZ4 declined to the float-plane codec (ops/fpcodec.py);
-    raw allocations carry no element type and are not offered. ``"auto"``
-    also offers everything else, the other registered tensors (CUDA or CPU)
-    and every tracked raw allocation, at the element size a probe of each
-    block's bytes finds, or raw where it finds none. Digests are of the raw
+    tensors that LZ4 declined to the float-plane codec (ops/fpcodec.py) and
+    those of 1-byte float tensors (the float8 family, ``float8_e8m0fnu``) to
+    the byte-plane codec (ops/bytecodec.py); raw allocations carry no element
+    type and are not offered. ``"auto"`` also offers everything else, the
+    other registered tensors (CUDA or CPU) and every tracked raw allocation,
+    at the element size, 2 or 4, a probe of each block's bytes finds, or raw
+    where it finds none; the probe does not look for 1-byte elements yet, so
+    untyped fp8 memory is not found. Digests are of the raw
     blocks, so the manifest is the same whatever the option, and restore
     needs no flag: a stored container names its codec."""
     from ..ops import devcodec, fpcodec, rawmem
@@ -332,7 +335,7 @@ def capture_manifest(store: Any, float_codec: Any = False) -> bytes:
     untyped = fpcodec.AUTO if float_codec == "auto" else 0
 
     def hint(t: Any) -> int:
-        fits = float_codec and t.dtype.is_floating_point and t.element_size() in (2, 4)
+        fits = float_codec and t.dtype.is_floating_point and t.element_size() in (1, 2, 4)
         return t.element_size() if fits else untyped
 
     def entry_for(nbytes: int, **extra: Any) -> dict:

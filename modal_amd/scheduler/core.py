@@ -1400,7 +1400,8 @@ class Scheduler:
         of digests; unchanged blocks of a later snapshot are stored once.
 
         float_codec=True (needs block_addressed): blocks of float tensors
-        that LZ4 declined are stored as MAFP10 containers (ops/fpcodec.py).
+        that LZ4 declined are stored as MAFP10 containers (ops/fpcodec.py),
+        those of fp8 tensors as MAFB10 containers (ops/bytecodec.py).
         float_codec="auto" also offers the blocks of every other tensor and
         of tracked raw allocations, at the element size found in their bytes."""
         if float_codec not in (False, True, "auto"):
