@@ -81,9 +81,9 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
             lib.ma_fpz_encode.argtypes = (
                 [ptr] * 5 + [i32, ptr, i32, ptr, i32, ctypes.c_long, ptr]
             )
-            lib.ma_fpz_assemble.restype = ctypes.c_int
-            lib.ma_fpz_assemble.argtypes = (
-                [ptr] * 3 + [i32] + [ptr] * 5 + [i32] + [ptr] * 2 + [i32, ptr]
+            lib.ma_rank_assemble.restype = ctypes.c_int
+            lib.ma_rank_assemble.argtypes = (
+                [ptr] * 3 + [i32] + [ptr] * 5 + [ctypes.c_ulonglong, i32] + [ptr] * 2 + [i32, ptr]
             )
             lib.ma_fpz_decode.restype = ctypes.c_int
             lib.ma_fpz_decode.argtypes = [ptr] * 10 + [i32, ptr]
@@ -92,10 +92,6 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
             lib.ma_bytez_encode.restype = ctypes.c_int
             lib.ma_bytez_encode.argtypes = (
                 [ptr] * 6 + [i32, ptr, i32, ctypes.c_long, ptr]
-            )
-            lib.ma_bytez_assemble.restype = ctypes.c_int
-            lib.ma_bytez_assemble.argtypes = (
-                [ptr] * 3 + [i32] + [ptr] * 7 + [i32, ptr]
             )
             lib.ma_bytez_decode.restype = ctypes.c_int
             lib.ma_bytez_decode.argtypes = [ptr] * 9 + [i32, ptr]

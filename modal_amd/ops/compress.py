@@ -15,7 +15,7 @@ the only parser), the LZ4 launches in front of the shared encoder tail
 (``compress_spans_gpu``, the only device encoder) and the LZ4 decode launch
 (``decompress_run_gpu``). The segmented container under it is
 ops/container.py, which MAFP10 (ops/fpcodec.py) and MAFB10 (ops/bytecodec.py)
-stand on as well.
+stand on as well, through the rank-plane codec they share (ops/rankcodec.py).
 
 ``compress_buffer_gpu``/``compress_buffers_gpu`` (blobs) and ops/devcodec.py
 (snapshots) are thin callers of these, so their containers are byte-identical

@@ -3,7 +3,8 @@
 table with one length per 4 KiB segment of the raw bytes (0: stored raw), the
 segments back to back. What follows from that alone lives here once and
 imports no codec; a codec adds its magic, its own header fields and checks,
-and its kernels.
+and its kernels. What MAFP10 and MAFB10 share beyond this is the layer above,
+ops/rankcodec.py.
 """
 
 from __future__ import annotations

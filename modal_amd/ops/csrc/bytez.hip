@@ -9,7 +9,7 @@
 //   hist      per block: LDS histogram of all its bytes, one global merge
 //   rank      fpz_rank_kernel (fpz.hip), through ma_fpz_rank_counts
 //   encode    one wavefront per segment -> its stride slot + comp_lens
-//   assemble  header + order + seg_len table + segments
+//   assemble  rank_assemble_kernel (fpz.hip), given this magic and es = 1
 //   decode    one wavefront per segment of a run of containers
 //
 // Encode and decode run one wavefront per workgroup, so __syncthreads() is a
@@ -59,7 +59,6 @@
 #include "malz_common.h"
 #include "rank_common.h"
 
-#define BZ_HEADER_FIXED 276  // magic 6, raw_len 8, es 1, reserved 1, n_seg 4, order 256
 #define BZ_HIST_BLOCK 256
 #define BZ_HIST_GROUPS 64
 #define BZ_HIST_COPIES 16
@@ -68,9 +67,6 @@
 // 4096 bytes, a pad dword per 16, and the two dwords an unaligned 8-byte read
 // of the last code bytes may touch behind them
 #define BZ_IN_DWORDS (SEG_SIZE / 4 + SEG_SIZE / 64 + 4)
-
-extern "C" int ma_fpz_rank_counts(const void* counts, void* order, void* rank_of, int n_blocks,
-                                  void* stream);
 
 __device__ __forceinline__ int padw(int k) { return k + (k >> 4); }           // dword k
 __device__ __forceinline__ int padb(int i) { return i + ((i >> 6) << 2); }    // byte i
@@ -322,37 +318,6 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_encode_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// assemble
-// ---------------------------------------------------------------------------
-
-extern "C" __global__ __launch_bounds__(ASM_BLOCK) void bytez_assemble_kernel(
-    const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_src_off,
-    const uint8_t* __restrict__ stride_buf, int out_stride,
-    const int32_t* __restrict__ comp_lens, const int64_t* __restrict__ seg_off,
-    const int32_t* __restrict__ blk_first_seg, const int64_t* __restrict__ blk_raw_len,
-    const uint8_t* __restrict__ order, uint8_t* __restrict__ out,
-    const int64_t* __restrict__ blk_out_off, int blk_base) {
-  const int b = blk_base + blockIdx.y;
-  const int64_t out_off = blk_out_off[b];
-  if (out_off < 0) return;  // container not kept: nothing to assemble
-  const int64_t raw_len = blk_raw_len[b];
-  const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
-  uint8_t* blk_out = out + out_off;
-
-  if (blockIdx.x == 0 && threadIdx.x < WAVE) {
-    const int lane = threadIdx.x;
-    const uint64_t magic = 0x30314246414DULL;  // "MAFB10", little-endian
-    put_le(blk_out, magic, 6, lane);
-    put_le(blk_out + 6, (uint64_t)raw_len, 8, lane);
-    put_le(blk_out + 14, 1, 2, lane);  // es 1, then the reserved 0
-    put_le(blk_out + 16, (uint64_t)n_seg, 4, lane);
-    wave_copy(order + (int64_t)b * 256, blk_out + 20, 256, lane);
-  }
-  assemble_segments(blk_out + BZ_HEADER_FIXED, src + blk_src_off[b], stride_buf, out_stride,
-                    comp_lens, seg_off, blk_first_seg[b], raw_len, n_seg);
-}
-
-// ---------------------------------------------------------------------------
 // decode: one wavefront per segment of a run of containers
 // ---------------------------------------------------------------------------
 
@@ -491,22 +456,6 @@ extern "C" int ma_bytez_encode(const void* src, const void* blk_src_off,
                        (const int64_t*)blk_raw_len, (const int32_t*)blk_first_seg,
                        (const uint8_t*)rank_of, (uint8_t*)stride_buf, out_stride,
                        (int32_t*)comp_lens, base);
-  });
-}
-
-extern "C" int ma_bytez_assemble(const void* src, const void* blk_src_off,
-                                 const void* stride_buf, int out_stride,
-                                 const void* comp_lens, const void* seg_off,
-                                 const void* blk_first_seg, const void* blk_raw_len,
-                                 const void* order, void* out, const void* blk_out_off,
-                                 int n_blocks, void* stream) {
-  return launch_chunked(n_blocks, [&](int base, int ny) {
-    hipLaunchKernelGGL(bytez_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
-                       (hipStream_t)stream, (const uint8_t*)src,
-                       (const int64_t*)blk_src_off, (const uint8_t*)stride_buf, out_stride,
-                       (const int32_t*)comp_lens, (const int64_t*)seg_off,
-                       (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
-                       (const uint8_t*)order, (uint8_t*)out, (const int64_t*)blk_out_off, base);
   });
 }
 

@@ -8,10 +8,13 @@
 //   probe     per block: the histograms at es 2 AND 4 in one pass over the
 //             bytes, for callers that have to find the element size
 //   hist      per block: LDS histogram of the top bytes, one global merge
-//   rank      per block: 256 threads each find their byte's rank by counting
+//   rank      per block: 256 threads each find their byte's rank by counting;
+//             MAFB10 (bytez.hip) ranks with it too
 //   encode    one wavefront per segment -> its stride slot + comp_lens, the
 //             same tables the MALZ41 plan kernel (malz.hip) then scans
-//   assemble  header + order + seg_len table + segments, like malz_assemble
+//   assemble  rank_assemble_kernel: header + order + seg_len table +
+//             segments, like malz_assemble; the one assemble kernel of MAFP10
+//             and MAFB10, which gives it its magic and es = 1
 //   decode    one wavefront per segment of a run of containers
 //
 // Encode and decode run one wavefront per workgroup, so __syncthreads() is a
@@ -32,7 +35,6 @@
 #include "malz_common.h"
 #include "rank_common.h"
 
-#define FPZ_HEADER_FIXED 276  // magic 6, raw_len 8, es 1, reserved 1, n_seg 4, order 256
 #define HIST_BLOCK 256
 #define HIST_GROUPS 64
 #define HIST_COPIES 8
@@ -318,15 +320,16 @@ extern "C" __global__ __launch_bounds__(WAVE) void fpz_encode_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// assemble
+// assemble: MAFP10 and MAFB10 containers (bytez.hip encodes the segments of
+// the latter), which differ in the magic and in the value of es
 // ---------------------------------------------------------------------------
 
-extern "C" __global__ __launch_bounds__(ASM_BLOCK) void fpz_assemble_kernel(
+extern "C" __global__ __launch_bounds__(ASM_BLOCK) void rank_assemble_kernel(
     const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_src_off,
     const uint8_t* __restrict__ stride_buf, int out_stride,
     const int32_t* __restrict__ comp_lens, const int64_t* __restrict__ seg_off,
     const int32_t* __restrict__ blk_first_seg, const int64_t* __restrict__ blk_raw_len,
-    const uint8_t* __restrict__ order, int es,
+    const uint8_t* __restrict__ order, uint64_t magic, int es,
     uint8_t* __restrict__ out, const int64_t* __restrict__ blk_out_off, int blk_base) {
   const int b = blk_base + blockIdx.y;
   const int64_t out_off = blk_out_off[b];
@@ -337,14 +340,13 @@ extern "C" __global__ __launch_bounds__(ASM_BLOCK) void fpz_assemble_kernel(
 
   if (blockIdx.x == 0 && threadIdx.x < WAVE) {
     const int lane = threadIdx.x;
-    const uint64_t magic = 0x30315046414DULL;  // "MAFP10", little-endian
-    put_le(blk_out, magic, 6, lane);
+    put_le(blk_out, magic, 6, lane);  // the six magic bytes, little-endian
     put_le(blk_out + 6, (uint64_t)raw_len, 8, lane);
     put_le(blk_out + 14, (uint64_t)es, 2, lane);  // es, then the reserved 0
     put_le(blk_out + 16, (uint64_t)n_seg, 4, lane);
     wave_copy(order + (int64_t)b * 256, blk_out + 20, 256, lane);
   }
-  assemble_segments(blk_out + FPZ_HEADER_FIXED, src + blk_src_off[b], stride_buf, out_stride,
+  assemble_segments(blk_out + RANK_HEADER_FIXED, src + blk_src_off[b], stride_buf, out_stride,
                     comp_lens, seg_off, blk_first_seg[b], raw_len, n_seg);
 }
 
@@ -505,20 +507,21 @@ extern "C" int ma_fpz_encode(const void* src, const void* blk_src_off,
   });
 }
 
-extern "C" int ma_fpz_assemble(const void* src, const void* blk_src_off,
-                               const void* stride_buf, int out_stride,
-                               const void* comp_lens, const void* seg_off,
-                               const void* blk_first_seg, const void* blk_raw_len,
-                               const void* order, int es, void* out,
-                               const void* blk_out_off, int n_blocks, void* stream) {
-  if (es != 2 && es != 4) return (int)hipErrorInvalidValue;
+// magic: the container's six magic bytes as a little-endian integer.
+extern "C" int ma_rank_assemble(const void* src, const void* blk_src_off,
+                                const void* stride_buf, int out_stride,
+                                const void* comp_lens, const void* seg_off,
+                                const void* blk_first_seg, const void* blk_raw_len,
+                                const void* order, unsigned long long magic, int es, void* out,
+                                const void* blk_out_off, int n_blocks, void* stream) {
+  if (es != 1 && es != 2 && es != 4) return (int)hipErrorInvalidValue;
   return launch_chunked(n_blocks, [&](int base, int ny) {
-    hipLaunchKernelGGL(fpz_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
+    hipLaunchKernelGGL(rank_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
                        (hipStream_t)stream, (const uint8_t*)src,
                        (const int64_t*)blk_src_off, (const uint8_t*)stride_buf, out_stride,
                        (const int32_t*)comp_lens, (const int64_t*)seg_off,
                        (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
-                       (const uint8_t*)order, es, (uint8_t*)out,
+                       (const uint8_t*)order, (uint64_t)magic, es, (uint8_t*)out,
                        (const int64_t*)blk_out_off, base);
   });
 }

@@ -1,10 +1,18 @@
-// Shared by the rank codecs (fpz.hip, bytez.hip) for gfx950: how a segment's
-// elements are split among the lanes of its wavefront, wavefront sums and
-// scans, and the copy of a decoded segment from LDS to any destination.
+// Shared by the rank codecs (fpz.hip, bytez.hip) for gfx950: the size of the
+// header both containers have, the rank pass of fpz.hip that both use, how a
+// segment's elements are split among the lanes of its wavefront, wavefront
+// sums and scans, and the copy of a decoded segment from LDS to any
+// destination.
 
 #pragma once
 
 #include "malz_common.h"
+
+#define RANK_HEADER_FIXED 276  // magic 6, raw_len 8, es 1, reserved 1, n_seg 4, order 256
+
+// fpz.hip: the rank tables of histograms the caller already has.
+extern "C" int ma_fpz_rank_counts(const void* counts, void* order, void* rank_of, int n_blocks,
+                                  void* stream);
 
 // Elements per lane: ceil(m/64) rounded up to a multiple of 8, so a lane's
 // codes are whole bytes at every width. 32 for m = 2048, 16 for m = 1024.

@@ -17,9 +17,10 @@ hinted as 1-byte elements (``elem_size`` 1: fp8, e8m0 scales) to the
 byte-plane codec (ops/bytecodec.py, MAFB10); an object of no known element
 type (``fpcodec.AUTO``) has those blocks probed on the device for the element
 size, 2 or 4, at which the float-plane codec pays, if any (the probe does not
-look for element size 1 yet). The codecs stand on ops/container.py and their
-validators return headers that begin (raw_len, seg lens, payload offset):
-nothing here tells them apart.
+look for element size 1 yet). Those two are one codec, ops/rankcodec.py,
+under two formats, and ``_plane_codec`` picks the format by element size. All
+the codecs stand on ops/container.py and their validators return headers that
+begin (raw_len, seg lens, payload offset): nothing else here tells them apart.
 
 What this module adds to those is the block layer: digests, skipping blocks
 the CAS already has, the cached 64 MiB scratch with its out-of-memory
@@ -154,6 +155,12 @@ def verify_device(objects: Sequence[tuple[int, Sequence[tuple[str, int]]]]) -> N
             raise mismatch(oi, bi)
 
 
+def _plane_codec(es: int) -> Any:
+    """The rank-plane codec (a ``rankcodec.Format``) that takes blocks hinted
+    as ``es``-byte elements: MAFB10's at 1, MAFP10's at 2 and 4."""
+    return bytecodec.FORMAT if es == 1 else fpcodec.FORMAT
+
+
 def _spans(nbytes: int, block_size: int) -> list[tuple[int, int]]:
     return [(off, min(block_size, nbytes - off)) for off in range(0, nbytes, block_size)]
 
@@ -210,14 +217,11 @@ def _encode_window(
                     counts=mine[:, col].contiguous(),
                 )
                 containers.update(zip([left[k] for k in rows], z))
-    elif left and elem_size == 1:
-        containers.update(
-            zip(left, bytecodec.compress_spans_gpu(lib, ptr, [spans[i] for i in left], sc))
-        )
     elif left:
-        containers.update(
-            zip(left, fpcodec.compress_spans_gpu(lib, ptr, [spans[i] for i in left], elem_size, sc))
+        z = _plane_codec(elem_size).compress_spans_gpu(
+            lib, ptr, [spans[i] for i in left], elem_size, sc
         )
+        containers.update(zip(left, z))
     blocks = []
     for i, (off, ln) in enumerate(spans):
         if skip[i]:
@@ -411,10 +415,8 @@ def encode_host(
         es = elem_size
         if z is None and es == fpcodec.AUTO and ln >= COMPRESS_MIN:
             es = fpcodec.choose_elem_size(*fpcodec.probe_counts_cpu(block), ln)[0]
-        if z is None and es == 1 and ln >= BYTE_MIN:
-            z = bytecodec.compress_buffer(block)
-        elif z is None and es and ln >= COMPRESS_MIN:
-            z = fpcodec.compress_buffer(block, es)
+        if z is None and es and ln >= (BYTE_MIN if es == 1 else COMPRESS_MIN):
+            z = _plane_codec(es).compress_buffer(block, es)
         if z is not None:
             blocks.append(EncodedBlock(content_digest(block), ln, z, True))
         else:

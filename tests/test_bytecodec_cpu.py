@@ -79,18 +79,18 @@ def _with(at: int, new: bytes, size: int = len(HAND_CONTAINER)) -> bytes:
     return (z + bytes(size))[:size]
 
 
-@pytest.mark.parametrize(
-    "blob",
-    [
-        _with(14, b"\x02"),  # es
-        _with(21, b"\x3f"),  # order holds 0x3F twice
-        _with(bc.HEADER, struct.pack("<I", 1), bc.HEADER + 4 + 1),  # seg_len 1
-        _with(bc.HEADER, struct.pack("<I", 64), bc.HEADER + 4 + 64),  # seg_len == L
-        HAND_CONTAINER[:-1],
-        HAND_CONTAINER + b"\x00",
-    ],
-    ids=["es", "order", "seg_len_1", "seg_len_L", "truncated", "over_long"],
-)
+#: one container per rejection of the validator (test_rankcodec_cpu.py reads it too)
+MALFORMED = {
+    "es": _with(14, b"\x02"),
+    "order": _with(21, b"\x3f"),  # order holds 0x3F twice
+    "seg_len_1": _with(bc.HEADER, struct.pack("<I", 1), bc.HEADER + 4 + 1),
+    "seg_len_L": _with(bc.HEADER, struct.pack("<I", 64), bc.HEADER + 4 + 64),  # seg_len == L
+    "truncated": HAND_CONTAINER[:-1],
+    "over_long": HAND_CONTAINER + b"\x00",
+}
+
+
+@pytest.mark.parametrize("blob", list(MALFORMED.values()), ids=list(MALFORMED))
 def test_validator_rejects(blob):
     from modal_amd.ops import bytecodec
 

@@ -2,8 +2,10 @@
 GPU: grids of more rows than one launch takes, for either assemble kernel
 and the MAFP10 histogram and encode kernels; the encoder's tail under either
 header size with declined spans in the middle; runs of one codec in a
-snapshot of mixed blocks. Every comparison is exact, against numpy models
-that share no code with the kernels, in buffers with canaries around them."""
+snapshot of mixed blocks, the two rank formats next to each other among
+them, and the assemble kernel they share under either magic. Every
+comparison is exact, against numpy models that share no code with the
+kernels, in buffers with canaries around them."""
 
 from __future__ import annotations
 
@@ -33,7 +35,7 @@ def _feature():
     from modal_amd.ops import load_lib
 
     lib = load_lib(required=True)
-    for symbol in ("ma_malz_plan", "ma_malz_assemble", "ma_fpz_encode", "ma_fpz_assemble"):
+    for symbol in ("ma_malz_plan", "ma_malz_assemble", "ma_fpz_encode", "ma_rank_assemble"):
         getattr(lib, symbol)
     return lib
 
@@ -216,3 +218,56 @@ def test_decode_runs_of_one_codec_in_a_mixed_snapshot():
     with pytest.raises(ValueError) as err:
         devcodec.decode_to_device(broken, whole.data_ptr() + at, 6 * n, verify=True)
     assert str(err.value) == "snapshot blocks 2..3: MAFP10 container corrupt at segment 17 of the run"
+
+
+def test_the_two_rank_formats_side_by_side():
+    """MAFP10 es 2, MAFB10, MAFP10 es 4, MAFB10, raw, LZ4 in blocks of two
+    segments: every rank block is a run of its own, since its neighbours are
+    of the other format; and the one device encoder writes each block's
+    container, either header, as the numpy model does."""
+    import torch
+
+    import byte_corpus as bc
+    from modal_amd.ops import bytecodec, compress, devcodec, fpcodec, rankcodec
+
+    lib = _feature()
+    n = 8 * KiB
+    unit = np.random.default_rng(6).integers(0, 256, 1024, dtype=np.uint8).tobytes()
+    raws = [
+        fc.bf16_gauss(n, seed=84), bc.fp8(n, "float8_e4m3fn", 85), fc.fp32_gauss(n, seed=86),
+        bc.fp8(n, "float8_e4m3fn", 87), fc.random_bytes(n, seed=88), unit * 8,
+    ]
+    stored = [
+        fpcodec.compress_buffer_cpu(raws[0], 2), bytecodec.compress_buffer_cpu(raws[1]),
+        fpcodec.compress_buffer_cpu(raws[2], 4), bytecodec.compress_buffer_cpu(raws[3]),
+        None, compress.compress_buffer_cpu(raws[5]),
+    ]
+    assert [z is None for z in stored] == [False, False, False, False, True, False]
+    assert [z[:6] for z in stored if z] == [b"MAFP10", b"MAFB10", b"MAFP10", b"MAFB10", b"MALZ41"]
+    assert [z[14] for z in stored[:4]] == [2, 1, 4, 1]
+    blocks = [
+        (hashlib.sha256(raw).hexdigest(), n, raw if z is None else z, z is not None)
+        for raw, z in zip(raws, stored)
+    ]
+    whole = torch.full((GUARD + 6 * n + GUARD,), CANARY, dtype=torch.uint8, device="cuda")
+    assert whole.data_ptr() % 16 == 0
+    at = GUARD + 5
+    devcodec.decode_to_device(blocks, whole.data_ptr() + at, 6 * n, verify=True)
+    got = whole.cpu().numpy()
+    assert got[at : at + 6 * n].tobytes() == b"".join(raws)
+    assert (got[:at] == CANARY).all() and (got[at + 6 * n :] == CANARY).all()
+
+    assert bytecodec.validate_container(stored[3]).seg_lens[1] != 0
+    bad = bytearray(stored[3])
+    bad[bc.segment_offsets(stored[3])[1]] = 0  # the width byte of segment 1
+    broken = list(blocks)
+    broken[3] = blocks[3][:2] + (bytes(bad), True)
+    with pytest.raises(ValueError) as err:
+        devcodec.decode_to_device(broken, whole.data_ptr() + at, 6 * n, verify=True)
+    assert str(err.value) == "snapshot blocks 3..3: MAFB10 container corrupt at segment 1 of the run"
+
+    buf, spans = _upload(raws[:4], 4)
+    for fmt, es, mine in ((fpcodec.FORMAT, 2, [0]), (bytecodec.FORMAT, 1, [1, 3]), (fpcodec.FORMAT, 4, [2])):
+        ws = rankcodec.Workspace.for_lengths([n] * len(mine), rankcodec.HEADER_FIXED)
+        got = fmt.compress_spans_gpu(lib, buf.data_ptr(), [spans[i] for i in mine], es, ws)
+        assert [bytes(z) for z in got] == [stored[i] for i in mine], (fmt.label, es)
