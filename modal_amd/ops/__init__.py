@@ -75,6 +75,8 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
             lib.ma_fpz_rank.argtypes = [ptr] * 3 + [i32] + [ptr] * 3 + [i32, ptr]
             lib.ma_fpz_probe.restype = ctypes.c_int
             lib.ma_fpz_probe.argtypes = [ptr] * 4 + [i32, ptr]
+            lib.ma_rank_probe.restype = ctypes.c_int
+            lib.ma_rank_probe.argtypes = lib.ma_fpz_probe.argtypes
             lib.ma_fpz_rank_counts.restype = ctypes.c_int
             lib.ma_fpz_rank_counts.argtypes = [ptr] * 3 + [i32, ptr]
             lib.ma_fpz_encode.restype = ctypes.c_int

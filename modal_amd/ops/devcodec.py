@@ -15,10 +15,10 @@ An object the caller hints as float data (``elem_size`` 2 or 4) offers the
 blocks LZ4 declined to the float-plane codec (ops/fpcodec.py, MAFP10), one
 hinted as 1-byte elements (``elem_size`` 1: fp8, e8m0 scales) to the
 byte-plane codec (ops/bytecodec.py, MAFB10); an object of no known element
-type (``fpcodec.AUTO``) has those blocks probed on the device for the element
-size, 2 or 4, at which the float-plane codec pays, if any (the probe does not
-look for element size 1 yet). Those two are one codec, ops/rankcodec.py,
-under two formats, and ``_plane_codec`` picks the format by element size. All
+type (``fpcodec.AUTO``) has those blocks probed on the device (ops/probe.py)
+for the element size, 1, 2 or 4, at which one of the two pays, if any. Those
+two are one codec, ops/rankcodec.py, under two formats, and ``_plane_codec``
+picks the format by element size. All
 the codecs stand on ops/container.py and their validators return headers that
 begin (raw_len, seg lens, payload offset): nothing else here tells them apart.
 
@@ -41,7 +41,7 @@ from typing import Any, Callable, Iterator, NamedTuple, Optional, Sequence
 import numpy as np
 
 from ..scheduler.blobs import BLOCK_SIZE, BlobStore
-from . import bytecodec, compress, fpcodec, load_lib
+from . import bytecodec, compress, fpcodec, load_lib, probe
 from .container import SEG_SIZE, Workspace
 from .hashing import GPU_MIN_BYTES, content_digest, leaf_table, sha256_leaves_gpu, tree_roots
 from .staging import copy_from_device, copy_to_device
@@ -187,9 +187,10 @@ def _encode_window(
     codec on the same scratch (LZ4 first: a zero-filled float tensor is 0.4 %
     under LZ4 and 56 % under MAFP10), with ``elem_size`` 1 through the
     byte-plane codec, which also takes the blocks of BYTE_MIN bytes and more
-    that are too short for LZ4. With ``fpcodec.AUTO`` they are probed first and each goes
-    through the float-plane codec at the element size the probe found (2 or
-    4), or stays raw where it found none."""
+    that are too short for LZ4. With ``fpcodec.AUTO`` both kinds are probed
+    first and each block goes through the codec of the element size the probe
+    found (1, 2 or 4; a short block only at 1), or stays raw where it found
+    none."""
     tree = [i for i, d in enumerate(digests) if d is None]
     for i, d in zip(tree, _tree_digests(lib, ptr, [spans[i] for i in tree])):
         digests[i] = d
@@ -199,20 +200,23 @@ def _encode_window(
         zip(cand, compress.compress_spans_gpu(lib, ptr, [spans[i] for i in cand], sc))
     )
     left = [i for i in cand if containers[i] is None] if elem_size else []
-    if elem_size == 1:
+    if elem_size in (1, fpcodec.AUTO):
         left += [
             i for i, (_o, ln) in enumerate(spans) if BYTE_MIN <= ln < COMPRESS_MIN and not skip[i]
         ]
     if elem_size == fpcodec.AUTO and left:
         # one probe of all of them, then one encode per element size it
         # found, each on its rows of the probe's tables
-        found, tables = fpcodec.probe_spans_gpu(lib, ptr, [spans[i] for i in left])
-        for col, es in enumerate(fpcodec.ELEM_SIZES):
-            rows = [k for k, e in enumerate(found) if e == es]
+        found, tables = probe.probe_spans_gpu(lib, ptr, [spans[i] for i in left])
+        for col, es in enumerate(probe.ELEM_SIZES):
+            rows = [
+                k for k, e in enumerate(found)
+                if e == es and (es == 1 or spans[left[k]][1] >= COMPRESS_MIN)
+            ]
             if rows:
                 # the usual window is of one kind: no index tensor to upload
                 mine = tables if len(rows) == len(found) else tables[rows]
-                z = fpcodec.compress_spans_gpu(
+                z = _plane_codec(es).compress_spans_gpu(
                     lib, ptr, [spans[left[k]] for k in rows], es, sc,
                     counts=mine[:, col].contiguous(),
                 )
@@ -248,9 +252,9 @@ def iter_encode_device(
     neither compressed nor copied. ``elem_sizes`` has one entry per object:
     2 or 4 offers the blocks LZ4 declined to the float-plane codec
     (ops/fpcodec.py), 1 to the byte-plane codec (ops/bytecodec.py),
-    ``fpcodec.AUTO`` offers them to the float-plane codec at the element size,
-    2 or 4, a probe of their bytes finds (per block; none: raw), 0 does not;
-    digests are of the RAW block either way."""
+    ``fpcodec.AUTO`` offers them to whichever of the two a probe of their
+    bytes finds, at the element size, 1, 2 or 4, it finds (per block; none:
+    raw), 0 does not; digests are of the RAW block either way."""
     _check_block_size(block_size)
     if elem_sizes is None:
         elem_sizes = [0] * len(objects)
@@ -400,8 +404,8 @@ def encode_host(
     data: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0
 ) -> list[EncodedBlock]:
     """Same manifest from host bytes (CPU tensors, CPU-only processes).
-    ``fpcodec.AUTO`` runs the probe's numpy twin, which knows element sizes
-    2 and 4, on every block LZ4 declined."""
+    ``fpcodec.AUTO`` runs the probe's numpy twin (ops/probe.py: element sizes
+    1, 2 and 4) on every block LZ4 declined or was too short for."""
     _check_block_size(block_size)
     if elem_size not in _ELEM_SIZES:
         raise ValueError("elem_size is one of 0, 1, 2, 4, fpcodec.AUTO")
@@ -413,8 +417,8 @@ def encode_host(
         block = bytes(view[off : off + ln])
         z = compress_buffer(block) if ln >= COMPRESS_MIN else None
         es = elem_size
-        if z is None and es == fpcodec.AUTO and ln >= COMPRESS_MIN:
-            es = fpcodec.choose_elem_size(*fpcodec.probe_counts_cpu(block), ln)[0]
+        if z is None and es == fpcodec.AUTO and ln >= BYTE_MIN:
+            es = probe.choose_elem_size(*probe.probe_counts_cpu(block), ln)[0]
         if z is None and es and ln >= (BYTE_MIN if es == 1 else COMPRESS_MIN):
             z = _plane_codec(es).compress_buffer(block, es)
         if z is not None:

@@ -323,9 +323,9 @@ def capture_manifest(store: Any, float_codec: Any = False) -> bytes:
     the byte-plane codec (ops/bytecodec.py); raw allocations carry no element
     type and are not offered. ``"auto"`` also offers everything else, the
     other registered tensors (CUDA or CPU) and every tracked raw allocation,
-    at the element size, 2 or 4, a probe of each block's bytes finds, or raw
-    where it finds none; the probe does not look for 1-byte elements yet, so
-    untyped fp8 memory is not found. Digests are of the raw
+    at the element size, 1, 2 or 4, a probe of each block's bytes finds
+    (ops/probe.py), or raw where it finds none, so an fp8 KV cache in a raw
+    allocation reaches the byte-plane codec. Digests are of the raw
     blocks, so the manifest is the same whatever the option, and restore
     needs no flag: a stored container names its codec."""
     from ..ops import devcodec, fpcodec, rawmem

@@ -8,7 +8,8 @@ compressible, no dedup), "random" (incompressible) and, when named, "bf16"
 (N(0,1) weights as bfloat16: LZ4 stores them raw, --float-codec offers them
 to the float-plane codec) and "rawbf16" (the same bytes held in a tracked raw
 allocation, ops/rawmem.py, registered as no tensor: only --float-codec auto
-reaches them) -- capture + restore through both paths, N timed
+reaches them) and "rawfp8" (N(0,1) as float8_e4m3fn in such an allocation: the
+probe has to find element size 1) -- capture + restore through both paths, N timed
 runs after one warm-up, median and min-max of host wall time around work
 that ends in torch.cuda.synchronize(). v2 also reports the bytes the CAS
 stored, the time of a second capture (every block already present), and the
@@ -17,7 +18,7 @@ tensor of --tail-bytes.
 
     python scripts/prof_snapshot.py --size-mib 1024 --runs 5
     python scripts/prof_snapshot.py --kinds bf16 --float-codec
-    python scripts/prof_snapshot.py --kinds rawbf16,random --float-codec auto
+    python scripts/prof_snapshot.py --kinds rawbf16,rawfp8,random --float-codec auto
 """
 
 from __future__ import annotations
@@ -45,6 +46,8 @@ def make_tensor(kind: str, nbytes: int) -> torch.Tensor:
     gen = torch.Generator(device="cuda").manual_seed(1234)
     if kind == "bf16":
         return torch.randn(nbytes // 2, device="cuda", generator=gen).to(torch.bfloat16)
+    if kind == "fp8":
+        return torch.randn(nbytes, device="cuda", generator=gen).to(torch.float8_e4m3fn)
     if kind == "random":
         return torch.randint(0, 256, (nbytes,), dtype=torch.uint8, device="cuda", generator=gen)
     if kind == "distinct":
@@ -122,12 +125,14 @@ def check(t: torch.Tensor, raw: bool = False) -> None:
         _copy_d2d(got.data_ptr(), ptr, size)
     else:
         got = gs.restored_tensor("w")
-    assert got.is_cuda and torch.equal(got, t), "restore changed the bytes"
+    # bytes, not values: float8 has no equality kernel
+    same = got.dtype == t.dtype and torch.equal(got.view(torch.uint8), t.view(torch.uint8))
+    assert got.is_cuda and same, "restore changed the bytes"
 
 
 def run_kind(kind: str, nbytes: int, runs: int, float_codec: object = False) -> dict:
-    raw = kind == "rawbf16"
-    t = make_tensor("bf16" if raw else kind, nbytes)
+    raw = kind in ("rawbf16", "rawfp8")
+    t = make_tensor(kind.removeprefix("raw"), nbytes)
     times: dict[str, list] = {k: [] for k in ("v1_capture", "v1_restore", "v2_capture", "v2_restore", "v2_second_capture")}
     stored = 0
     for it in range(runs + 1):  # run 0 is the warm-up
@@ -178,7 +183,7 @@ def main() -> None:
     ap.add_argument("--float-codec", nargs="?", const=True, default=False, choices=["auto"],
                     help="capture_manifest(float_codec=True): MAFP10 for float tensors; "
                          "'--float-codec auto': also for untyped tensors and raw allocations, "
-                         "at the element size probed in their bytes")
+                         "at the element size (1, 2 or 4) probed in their bytes")
     args = ap.parse_args()
     for kind in args.kinds.split(","):
         print(json.dumps(run_kind(kind, args.size_mib * MiB, args.runs, args.float_codec)), flush=True)
