@@ -97,6 +97,10 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
             )
             lib.ma_bytez_decode.restype = ctypes.c_int
             lib.ma_bytez_decode.argtypes = [ptr] * 9 + [i32, ptr]
+            lib.ma_ricez_encode.restype = ctypes.c_int
+            lib.ma_ricez_encode.argtypes = lib.ma_fpz_encode.argtypes
+            lib.ma_ricez_decode.restype = ctypes.c_int
+            lib.ma_ricez_decode.argtypes = lib.ma_fpz_decode.argtypes
             from .rawmem import _bind as _bind_rawmem
 
             _bind_rawmem(lib)

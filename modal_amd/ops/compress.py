@@ -79,13 +79,15 @@ def is_compressed(blob: bytes) -> bool:
 
 def codec_of(blob: bytes) -> Any:
     """The module that reads a stored container: fpcodec for the MAFP10 magic,
-    bytecodec for MAFB10, this one otherwise. Whether a blob is compressed at
+    bytecodec for MAFB10, ricecodec for MARC10, this one otherwise. Whether a blob is compressed at
     all is out of band (the ``.z`` suffix), so the magic only has to tell our
     formats apart."""
-    from . import bytecodec, compress, fpcodec  # here, so that importing this module needs no numpy
+    from . import bytecodec, compress, fpcodec, ricecodec  # here: importing this module needs no numpy
 
     if fpcodec.is_fp_container(blob):
         return fpcodec
+    if ricecodec.is_rice_container(blob):
+        return ricecodec
     return bytecodec if bytecodec.is_byte_container(blob) else compress
 
 

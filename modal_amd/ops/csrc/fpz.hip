@@ -38,21 +38,6 @@
 #define HIST_BLOCK 256
 #define HIST_GROUPS 64
 #define HIST_COPIES 8
-// mis (<= 3) + 4096 bytes, rounded up to dwords, plus a pad dword per 16
-#define IN_DWORDS (((SEG_SIZE + 3 + 3) / 4) * 17 / 16 + 2)
-
-__device__ __forceinline__ int pad(int x) { return x + ((x >> 6) << 2); }
-
-// len bytes at src -> LDS, padded; byte i of the segment is in[pad(mis + i)].
-// Every dword loaded holds at least one of the segment's own bytes.
-__device__ __forceinline__ int stage_in(const uint8_t* __restrict__ src, int len,
-                                        uint32_t* in32, int lane) {
-  const int mis = (int)(reinterpret_cast<uintptr_t>(src) & 3);
-  const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src - mis);
-  const int n_dw = (mis + len + 3) >> 2;
-  for (int k = lane; k < n_dw; k += WAVE) in32[k + (k >> 4)] = s1[k];
-  return mis;
-}
 
 // ---------------------------------------------------------------------------
 // histogram and rank

@@ -1,5 +1,5 @@
-// Shared by the rank codecs (fpz.hip, bytez.hip) for gfx950: the size of the
-// header both containers have, the rank pass of fpz.hip that both use, how a
+// Shared by the rank codecs (fpz.hip, bytez.hip, ricez.hip) for gfx950: the size of the
+// header their containers have, the rank pass of fpz.hip that both use, how a
 // segment's elements are split among the lanes of its wavefront, wavefront
 // sums and scans, and the copy of a decoded segment from LDS to any
 // destination.
@@ -13,6 +13,23 @@
 // fpz.hip: the rank tables of histograms the caller already has.
 extern "C" int ma_fpz_rank_counts(const void* counts, void* order, void* rank_of, int n_blocks,
                                   void* stream);
+
+// Staging of fpz.hip and ricez.hip (the comment at the top of fpz.hip):
+// mis (<= 3) + 4096 bytes, rounded up to dwords, plus a pad dword per 16
+#define IN_DWORDS (((SEG_SIZE + 3 + 3) / 4) * 17 / 16 + 2)
+
+__device__ __forceinline__ int pad(int x) { return x + ((x >> 6) << 2); }
+
+// len bytes at src -> LDS, padded; byte i of the segment is in[pad(mis + i)].
+// Every dword loaded holds at least one of the segment's own bytes.
+__device__ __forceinline__ int stage_in(const uint8_t* __restrict__ src, int len,
+                                        uint32_t* in32, int lane) {
+  const int mis = (int)(reinterpret_cast<uintptr_t>(src) & 3);
+  const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src - mis);
+  const int n_dw = (mis + len + 3) >> 2;
+  for (int k = lane; k < n_dw; k += WAVE) in32[k + (k >> 4)] = s1[k];
+  return mis;
+}
 
 // Elements per lane: ceil(m/64) rounded up to a multiple of 8, so a lane's
 // codes are whole bytes at every width. 32 for m = 2048, 16 for m = 1024.

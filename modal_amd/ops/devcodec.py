@@ -41,7 +41,7 @@ from typing import Any, Callable, Iterator, NamedTuple, Optional, Sequence
 import numpy as np
 
 from ..scheduler.blobs import BLOCK_SIZE, BlobStore
-from . import bytecodec, compress, fpcodec, load_lib, probe
+from . import bytecodec, compress, fpcodec, load_lib, probe, ricecodec
 from .container import SEG_SIZE, Workspace
 from .hashing import GPU_MIN_BYTES, content_digest, leaf_table, sha256_leaves_gpu, tree_roots
 from .staging import copy_from_device, copy_to_device
@@ -54,6 +54,7 @@ COMPRESS_MIN = BlobStore.COMPRESS_MIN
 BYTE_MIN = 64 * 1024
 RUN_MAX_BLOCKS = 128  # decode: blocks per decompress launch, at most
 _ELEM_SIZES = (0, 1, *fpcodec.ELEM_SIZES, fpcodec.AUTO)  # what an element size hint may be
+_RANK_CODINGS = ("fixed", "rice")  # how a rank-plane codec codes the ranks
 _TREE_GROUP = 8  # verify: full blocks whose leaves share one hash dispatch
 
 
@@ -155,10 +156,23 @@ def verify_device(objects: Sequence[tuple[int, Sequence[tuple[str, int]]]]) -> N
             raise mismatch(oi, bi)
 
 
-def _plane_codec(es: int) -> Any:
+def _plane_codec(es: int, rank_coding: str = "fixed") -> Any:
     """The rank-plane codec (a ``rankcodec.Format``) that takes blocks hinted
-    as ``es``-byte elements: MAFB10's at 1, MAFP10's at 2 and 4."""
+    as ``es``-byte elements: MAFB10's at 1, MAFP10's at 2 and 4, and with
+    ``rank_coding`` "rice" MARC10's (ops/ricecodec.py) at all three."""
+    if rank_coding == "rice":
+        return ricecodec.FORMAT
     return bytecodec.FORMAT if es == 1 else fpcodec.FORMAT
+
+
+def _check_rank_coding(rank_coding: str) -> None:
+    if rank_coding not in _RANK_CODINGS:
+        raise ValueError(f'rank_coding is "fixed" or "rice", got {rank_coding!r}')
+
+
+def _estimator(rank_coding: str) -> Any:
+    """What the element-size probe compares under ``rank_coding``."""
+    return ricecodec.estimate if rank_coding == "rice" else fpcodec._estimate
 
 
 def _spans(nbytes: int, block_size: int) -> list[tuple[int, int]]:
@@ -180,6 +194,7 @@ def _check_block_size(block_size: int) -> None:
 def _encode_window(
     lib: Any, sc: Workspace, ptr: int, spans: Sequence[tuple[int, int]],
     digests: list, known: Optional[Callable[[str], bool]], elem_size: int = 0,
+    rank_coding: str = "fixed",
 ) -> list[EncodedBlock]:
     """Blocks of one window (<= WINDOW source bytes) of the object at ptr.
     ``digests`` holds the short blocks' digests; full blocks are None. With
@@ -190,7 +205,8 @@ def _encode_window(
     that are too short for LZ4. With ``fpcodec.AUTO`` both kinds are probed
     first and each block goes through the codec of the element size the probe
     found (1, 2 or 4; a short block only at 1), or stays raw where it found
-    none."""
+    none. ``rank_coding`` "rice" puts MARC10 where MAFP10 and MAFB10 stand and
+    its estimate into the probe; nothing else changes."""
     tree = [i for i, d in enumerate(digests) if d is None]
     for i, d in zip(tree, _tree_digests(lib, ptr, [spans[i] for i in tree])):
         digests[i] = d
@@ -207,7 +223,9 @@ def _encode_window(
     if elem_size == fpcodec.AUTO and left:
         # one probe of all of them, then one encode per element size it
         # found, each on its rows of the probe's tables
-        found, tables = probe.probe_spans_gpu(lib, ptr, [spans[i] for i in left])
+        found, tables = probe.probe_spans_gpu(
+            lib, ptr, [spans[i] for i in left], _estimator(rank_coding)
+        )
         for col, es in enumerate(probe.ELEM_SIZES):
             rows = [
                 k for k, e in enumerate(found)
@@ -216,13 +234,13 @@ def _encode_window(
             if rows:
                 # the usual window is of one kind: no index tensor to upload
                 mine = tables if len(rows) == len(found) else tables[rows]
-                z = _plane_codec(es).compress_spans_gpu(
+                z = _plane_codec(es, rank_coding).compress_spans_gpu(
                     lib, ptr, [spans[left[k]] for k in rows], es, sc,
                     counts=mine[:, col].contiguous(),
                 )
                 containers.update(zip([left[k] for k in rows], z))
     elif left:
-        z = _plane_codec(elem_size).compress_spans_gpu(
+        z = _plane_codec(elem_size, rank_coding).compress_spans_gpu(
             lib, ptr, [spans[i] for i in left], elem_size, sc
         )
         containers.update(zip(left, z))
@@ -240,7 +258,7 @@ def _encode_window(
 def iter_encode_device(
     objects: Sequence[tuple[int, int]], *, block_size: int = BLOCK_SIZE,
     known: Optional[Callable[[str], bool]] = None,
-    elem_sizes: Optional[Sequence[int]] = None,
+    elem_sizes: Optional[Sequence[int]] = None, rank_coding: str = "fixed",
 ) -> Iterator[tuple[int, EncodedBlock]]:
     """Encode several device objects ``(ptr, nbytes)``; yields
     ``(object index, block)`` in object then block order, a window at a time,
@@ -254,8 +272,11 @@ def iter_encode_device(
     (ops/fpcodec.py), 1 to the byte-plane codec (ops/bytecodec.py),
     ``fpcodec.AUTO`` offers them to whichever of the two a probe of their
     bytes finds, at the element size, 1, 2 or 4, it finds (per block; none:
-    raw), 0 does not; digests are of the RAW block either way."""
+    raw), 0 does not; digests are of the RAW block either way.
+    ``rank_coding`` "rice" has those codecs write Rice-coded MARC10 containers
+    (ops/ricecodec.py) where "fixed", the default, writes MAFP10 and MAFB10."""
     _check_block_size(block_size)
+    _check_rank_coding(rank_coding)
     if elem_sizes is None:
         elem_sizes = [0] * len(objects)
     if len(elem_sizes) != len(objects) or any(es not in _ELEM_SIZES for es in elem_sizes):
@@ -285,16 +306,21 @@ def iter_encode_device(
                         blocks.append(EncodedBlock(content_digest(data, gpu=False), ln, data, False))
                 else:
                     digests = [short.get((oi, w0 + k)) for k in range(len(wspans))]
-                    blocks = _encode_window(lib, sc, ptr, wspans, digests, known, elem_sizes[oi])
+                    blocks = _encode_window(
+                        lib, sc, ptr, wspans, digests, known, elem_sizes[oi], rank_coding
+                    )
             for blk in blocks:
                 yield oi, blk
 
 
 def encode_device(
-    ptr: int, nbytes: int, *, block_size: int = BLOCK_SIZE, elem_size: int = 0
+    ptr: int, nbytes: int, *, block_size: int = BLOCK_SIZE, elem_size: int = 0,
+    rank_coding: str = "fixed",
 ) -> list[EncodedBlock]:
     """CAS blocks of the ``nbytes`` at device pointer ``ptr``."""
-    it = iter_encode_device([(ptr, nbytes)], block_size=block_size, elem_sizes=[elem_size])
+    it = iter_encode_device(
+        [(ptr, nbytes)], block_size=block_size, elem_sizes=[elem_size], rank_coding=rank_coding
+    )
     return [blk for _oi, blk in it]
 
 
@@ -305,12 +331,14 @@ def _tensor_span(t: Any) -> tuple[int, int]:
 
 
 def encode_tensor(
-    t: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0
+    t: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0, rank_coding: str = "fixed"
 ) -> list[EncodedBlock]:
     """``elem_size`` is the caller's to give: it is not inferred from t's
     dtype (``fpcodec.AUTO`` infers it from the bytes)."""
     ptr, nbytes = _tensor_span(t)
-    return encode_device(ptr, nbytes, block_size=block_size, elem_size=elem_size)
+    return encode_device(
+        ptr, nbytes, block_size=block_size, elem_size=elem_size, rank_coding=rank_coding
+    )
 
 
 # ---------------------------------------------------------------------------
@@ -401,12 +429,13 @@ def decode_tensor(blocks: Sequence, t: Any, *, verify: bool = True) -> None:
 
 
 def encode_host(
-    data: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0
+    data: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0, rank_coding: str = "fixed"
 ) -> list[EncodedBlock]:
     """Same manifest from host bytes (CPU tensors, CPU-only processes).
     ``fpcodec.AUTO`` runs the probe's numpy twin (ops/probe.py: element sizes
     1, 2 and 4) on every block LZ4 declined or was too short for."""
     _check_block_size(block_size)
+    _check_rank_coding(rank_coding)
     if elem_size not in _ELEM_SIZES:
         raise ValueError("elem_size is one of 0, 1, 2, 4, fpcodec.AUTO")
     from .compress import compress_buffer
@@ -418,9 +447,11 @@ def encode_host(
         z = compress_buffer(block) if ln >= COMPRESS_MIN else None
         es = elem_size
         if z is None and es == fpcodec.AUTO and ln >= BYTE_MIN:
-            es = probe.choose_elem_size(*probe.probe_counts_cpu(block), ln)[0]
+            es = probe.choose_elem_size(
+                *probe.probe_counts_cpu(block), ln, _estimator(rank_coding)
+            )[0]
         if z is None and es and ln >= (BYTE_MIN if es == 1 else COMPRESS_MIN):
-            z = _plane_codec(es).compress_buffer(block, es)
+            z = _plane_codec(es, rank_coding).compress_buffer(block, es)
         if z is not None:
             blocks.append(EncodedBlock(content_digest(block), ln, z, True))
         else:

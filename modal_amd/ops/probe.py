@@ -42,16 +42,20 @@ def probe_counts_cpu(data: Any) -> tuple[Any, Any, Any]:
     )
 
 
-def _choose(counts1: Any, counts2: Any, counts4: Any, raw_len: Any) -> tuple[Any, Any]:
+def _choose(
+    counts1: Any, counts2: Any, counts4: Any, raw_len: Any, estimate: Any = _estimate
+) -> tuple[Any, Any]:
     tables = {1: counts1, 2: counts2, 4: counts4}
-    ests = np.stack([_estimate(tables[es], raw_len, es) for es in _TIE_ORDER])
+    ests = np.stack([estimate(tables[es], raw_len, es) for es in _TIE_ORDER])
     pick = ests.argmin(axis=0)  # the first minimum: 2, then 4, then 1
     est = ests.min(axis=0)
     es = np.asarray(_TIE_ORDER)[pick]
     return np.where(worth_keeping(est, np.asarray(raw_len, dtype=np.int64)), es, 0), est
 
 
-def choose_elem_size(counts1: Any, counts2: Any, counts4: Any, raw_len: int) -> tuple[int, int]:
+def choose_elem_size(
+    counts1: Any, counts2: Any, counts4: Any, raw_len: int, estimate: Any = _estimate
+) -> tuple[int, int]:
     """(es, estimate): the element size, 1, 2 or 4, at which a rank-plane
     container of a block of ``raw_len`` bytes with these three histograms comes
     out smallest, and the payload estimated for it; ``es`` is 0 when even that
@@ -65,12 +69,18 @@ def choose_elem_size(counts1: Any, counts2: Any, counts4: Any, raw_len: int) -> 
     MAFP10's: a full segment's ``m = 4096`` is a multiple of 8 as 2048 and
     1024 are, and MAFB10's encoder picks its widths by the same rule. At es 1
     every length is a whole number of elements, so the short last segment is
-    never stored raw for being odd."""
-    es, est = _choose(counts1, counts2, counts4, raw_len)
+    never stored raw for being odd.
+
+    ``estimate(counts, raw_len, es)`` is the fixed-width rule above unless the
+    caller codes ranks another way and gives its own
+    (``ricecodec.estimate``); the ties and the 5 % rule are the same."""
+    es, est = _choose(counts1, counts2, counts4, raw_len, estimate)
     return int(es), int(est)
 
 
-def probe_spans_gpu(lib: Any, base: int, spans: Sequence[tuple[int, int]]) -> tuple[list, Any]:
+def probe_spans_gpu(
+    lib: Any, base: int, spans: Sequence[tuple[int, int]], estimate: Any = _estimate
+) -> tuple[list, Any]:
     """``choose_elem_size`` for the device bytes ``(base + offset, raw_len)``
     of every span: (the element size per span, 0 where no rank-plane container
     would pay; the probe's tables, a ``len(spans) x 3 x 256`` int32 device
@@ -94,5 +104,7 @@ def probe_spans_gpu(lib: Any, base: int, spans: Sequence[tuple[int, int]]) -> tu
         "rank probe kernel",
     )
     host = counts.cpu().numpy().view(np.uint32)  # syncs: the tables may be freed
-    es, _est = _choose(host[:, 0], host[:, 1], host[:, 2], [ln for _off, ln in spans])
+    es, _est = _choose(
+        host[:, 0], host[:, 1], host[:, 2], [ln for _off, ln in spans], estimate
+    )
     return es.tolist(), counts

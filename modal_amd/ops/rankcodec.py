@@ -76,6 +76,7 @@ class Format:
     encode_entry: str  # segments -> stride slots,
     decode_entry: str  # a run of containers -> raw bytes
     es_in_abi: bool  # those entries take the element size (False: they know it)
+    min_hi: int = 2  # the fewest bytes a coded segment has after its low bytes
 
     def __post_init__(self) -> None:
         # a full segment is a whole number of elements: validator and kernels count on it
@@ -119,7 +120,7 @@ class Format:
         if n_seg and coded[-1] and L[-1] % es:
             raise ValueError(f"{what}: coded segment is not a whole number of elements")
         lo = (L // es) * (es - 1)
-        if np.any(coded & ((seg_lens < lo + 2) | (seg_lens >= L))):
+        if np.any(coded & ((seg_lens < lo + self.min_hi) | (seg_lens >= L))):
             raise ValueError(f"{what}: segment seg_len out of range")
         container.check_size(blob, off, int(np.where(coded, seg_lens, L).sum()), what)
         return Header(hdr_raw, seg_lens.astype(np.int32), off, es, order)
@@ -250,6 +251,17 @@ class Format:
     # GPU paths
     # -----------------------------------------------------------------------
 
+    def _launch_rank(
+        self, lib: Any, es: int, base: int, src_off: int, raw_len: int, counts: int,
+        *tables_and_stream: Any,
+    ) -> int:
+        """The histogram + rank launch of ``rank_entry`` at ``es``; a format
+        whose element sizes are ranked by different entries overrides it."""
+        es_arg = (es,) if self.es_in_abi else ()
+        return getattr(lib, self.rank_entry)(
+            base, src_off, raw_len, *es_arg, counts, *tables_and_stream
+        )
+
     def compress_spans_gpu(
         self, lib: Any, base: int, spans: Sequence[tuple[int, int]], es: int, ws: Workspace,
         counts: Any = None,
@@ -268,7 +280,6 @@ class Format:
         if not spans:
             return []
         stream = torch.cuda.current_stream().cuda_stream
-        es_arg = (es,) if self.es_in_abi else ()
         n_segs = np.array([-(-ln // SEG_SIZE) for _off, ln in spans], dtype=np.int64)
         ends_seg = np.cumsum(n_segs)
         if int(ends_seg[-1]) > ws.n_seg:
@@ -278,8 +289,8 @@ class Format:
         order_d, rank_d = tables[0], tables[1]
         if counts is None:
             counts = torch.zeros(len(spans) * 256, dtype=torch.int32, device="cuda")
-            rc = getattr(lib, self.rank_entry)(
-                base, src_off_d.data_ptr(), raw_d.data_ptr(), *es_arg, counts.data_ptr(),
+            rc = self._launch_rank(
+                lib, es, base, src_off_d.data_ptr(), raw_d.data_ptr(), counts.data_ptr(),
                 order_d.data_ptr(), rank_d.data_ptr(), len(spans), stream,
             )
         else:
@@ -292,6 +303,7 @@ class Format:
                 counts.data_ptr(), order_d.data_ptr(), rank_d.data_ptr(), len(spans), stream
             )
         container.check(rc, f"{self.label} histogram/rank kernels")
+        es_arg = (es,) if self.es_in_abi else ()
         container.check(
             getattr(lib, self.encode_entry)(
                 base, src_off_d.data_ptr(), raw_d.data_ptr(), first_d.data_ptr(),

@@ -309,7 +309,7 @@ def restore_payload(data: bytes, store: Any = None) -> dict:
 _RESTORE_CHUNK_BLOCKS = 8
 
 
-def capture_manifest(store: Any, float_codec: Any = False) -> bytes:
+def capture_manifest(store: Any, float_codec: Any = False, rank_coding: str = "fixed") -> bytes:
     """Block-addressed snapshot: every registered tensor and tracked raw
     allocation is cut into CAS blocks, hashed and compressed where it lives
     (CUDA memory on the GPU through ops/devcodec.py, CPU tensors on the
@@ -327,11 +327,17 @@ def capture_manifest(store: Any, float_codec: Any = False) -> bytes:
     (ops/probe.py), or raw where it finds none, so an fp8 KV cache in a raw
     allocation reaches the byte-plane codec. Digests are of the raw
     blocks, so the manifest is the same whatever the option, and restore
-    needs no flag: a stored container names its codec."""
+    needs no flag: a stored container names its codec.
+
+    ``rank_coding`` "rice" has those codecs Rice-code the ranks (MARC10,
+    ops/ricecodec.py) where "fixed", the default, packs them at a fixed width
+    (MAFP10, MAFB10): smaller containers from slower coding kernels."""
     from ..ops import devcodec, fpcodec, rawmem
 
     if float_codec not in (False, True, "auto"):
         raise ValueError(f'float_codec is False, True or "auto", got {float_codec!r}')
+    if rank_coding not in ("fixed", "rice"):
+        raise ValueError(f'rank_coding is "fixed" or "rice", got {rank_coding!r}')
     untyped = fpcodec.AUTO if float_codec == "auto" else 0
 
     def hint(t: Any) -> int:
@@ -370,7 +376,7 @@ def capture_manifest(store: Any, float_codec: Any = False) -> bytes:
             else:
                 # byte-level view: numpy() would reject bf16/fp8 dtypes
                 flat = src.reshape(-1).view(torch.uint8).numpy()
-                for blk in devcodec.encode_host(flat, elem_size=hint(t)):
+                for blk in devcodec.encode_host(flat, elem_size=hint(t), rank_coding=rank_coding):
                     add(entry, blk)
     lib = rawmem.load_lib()
     if lib is not None:
@@ -384,7 +390,9 @@ def capture_manifest(store: Any, float_codec: Any = False) -> bytes:
     if on_device:
         objects = [(ptr, nbytes) for _e, ptr, nbytes, _es, _k in on_device]
         hints = [es for _e, _ptr, _n, es, _k in on_device]
-        for oi, blk in devcodec.iter_encode_device(objects, known=store.has, elem_sizes=hints):
+        for oi, blk in devcodec.iter_encode_device(
+            objects, known=store.has, elem_sizes=hints, rank_coding=rank_coding
+        ):
             add(on_device[oi][0], blk)
     payload = {
         "version": 2,

@@ -1388,7 +1388,8 @@ class Scheduler:
 
     # -- worker GPU snapshots ---------------------------------------------
     async def worker_snapshot(
-        self, worker_id: int, block_addressed: bool = False, float_codec: Any = False
+        self, worker_id: int, block_addressed: bool = False, float_codec: Any = False,
+        rank_coding: str = "fixed",
     ) -> dict:
         """Capture a worker's snapshot-visible GPU state (registered
         tensors + tracked raw hipMalloc allocations + RNG) into the CAS.
@@ -1403,16 +1404,26 @@ class Scheduler:
         that LZ4 declined are stored as MAFP10 containers (ops/fpcodec.py),
         those of fp8 tensors as MAFB10 containers (ops/bytecodec.py).
         float_codec="auto" also offers the blocks of every other tensor and
-        of tracked raw allocations, at the element size found in their bytes."""
+        of tracked raw allocations, at the element size found in their bytes.
+
+        rank_coding="rice" (needs float_codec): those blocks are stored as
+        Rice-coded MARC10 containers (ops/ricecodec.py), a few points of raw
+        smaller; restore reads every format."""
         if float_codec not in (False, True, "auto"):
             raise InvalidError(f'float_codec is False, True or "auto", got {float_codec!r}')
         if float_codec and not block_addressed:
             raise InvalidError("float_codec needs block_addressed=True")
+        if rank_coding not in ("fixed", "rice"):
+            raise InvalidError(f'rank_coding is "fixed" or "rice", got {rank_coding!r}')
+        if rank_coding == "rice" and not float_codec:
+            raise InvalidError('rank_coding="rice" needs float_codec')
         w = self.pool.workers.get(int(worker_id))
         if w is None:
             raise NotFoundError(f"worker {worker_id} not connected")
         rpc = "snapshot_manifest" if block_addressed else "snapshot_state"
         params = {"float_codec": float_codec} if float_codec else None
+        if rank_coding != "fixed":
+            params["rank_coding"] = rank_coding
         data = await w.conn.call(rpc, params, timeout=300)
         blob_id = self.blob_store.put(data)
         return {"snapshot_id": blob_id}

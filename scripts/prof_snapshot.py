@@ -130,7 +130,8 @@ def check(t: torch.Tensor, raw: bool = False) -> None:
     assert got.is_cuda and same, "restore changed the bytes"
 
 
-def run_kind(kind: str, nbytes: int, runs: int, float_codec: object = False) -> dict:
+def run_kind(kind: str, nbytes: int, runs: int, float_codec: object = False,
+             rank_coding: str = "fixed") -> dict:
     raw = kind in ("rawbf16", "rawfp8")
     t = make_tensor(kind.removeprefix("raw"), nbytes)
     times: dict[str, list] = {k: [] for k in ("v1_capture", "v1_restore", "v2_capture", "v2_restore", "v2_second_capture")}
@@ -148,9 +149,9 @@ def run_kind(kind: str, nbytes: int, runs: int, float_codec: object = False) -> 
         try:
             store = BlobStore(root)
             reset(t, raw)
-            c2, manifest = timed(lambda: gs.capture_manifest(store, float_codec=float_codec))
+            c2, manifest = timed(lambda: gs.capture_manifest(store, float_codec=float_codec, rank_coding=rank_coding))
             stored = stored_bytes(root)
-            c2b, _ = timed(lambda: gs.capture_manifest(store, float_codec=float_codec))
+            c2b, _ = timed(lambda: gs.capture_manifest(store, float_codec=float_codec, rank_coding=rank_coding))
             assert stored_bytes(root) == stored
             drop(raw)
             r2, _ = timed(lambda: gs.restore_payload(manifest, store))
@@ -161,7 +162,7 @@ def run_kind(kind: str, nbytes: int, runs: int, float_codec: object = False) -> 
             for key, val in zip(times, (c1, r1, c2, r2, c2b)):
                 times[key].append(val)
     drop(raw)
-    out = {"kind": kind, "float_codec": float_codec, "nbytes": nbytes, "v1_payload_bytes": v1_bytes, "v2_stored_bytes": stored}
+    out = {"kind": kind, "float_codec": float_codec, "rank_coding": rank_coding, "nbytes": nbytes, "v1_payload_bytes": v1_bytes, "v2_stored_bytes": stored}
     out.update({key: summary(vals) for key, vals in times.items()})
     return out
 
@@ -184,9 +185,13 @@ def main() -> None:
                     help="capture_manifest(float_codec=True): MAFP10 for float tensors; "
                          "'--float-codec auto': also for untyped tensors and raw allocations, "
                          "at the element size (1, 2 or 4) probed in their bytes")
+    ap.add_argument("--rank-coding", default="fixed", choices=["fixed", "rice"],
+                    help="with --float-codec: 'rice' stores Rice-coded MARC10 containers "
+                         "where 'fixed' stores MAFP10 and MAFB10")
     args = ap.parse_args()
     for kind in args.kinds.split(","):
-        print(json.dumps(run_kind(kind, args.size_mib * MiB, args.runs, args.float_codec)), flush=True)
+        print(json.dumps(run_kind(kind, args.size_mib * MiB, args.runs, args.float_codec,
+                                  args.rank_coding)), flush=True)
     print(json.dumps(tail_hash(args.tail_bytes)), flush=True)
 
 
