@@ -53,6 +53,8 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
                 ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
                 ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
             ]
+            lib.ma_lz4_compress_wave.restype = ctypes.c_int
+            lib.ma_lz4_compress_wave.argtypes = lib.ma_lz4_compress.argtypes
             lib.ma_lz4_decompress.restype = ctypes.c_int
             lib.ma_lz4_decompress.argtypes = [
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

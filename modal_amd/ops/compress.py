@@ -13,7 +13,10 @@ payload; the CPU reference codec (utils/lz4ref.py) serves GPU-less readers.
 What only MALZ41 knows lives here once: its header (``validate_container``,
 the only parser), the LZ4 launches in front of the shared encoder tail
 (``compress_spans_gpu``, the only device encoder) and the LZ4 decode launch
-(``decompress_run_gpu``). The segmented container under it is
+(``decompress_run_gpu``). ``lz_parser`` picks the kernel of those LZ4
+launches: "lane" (csrc/lz4.hip, the default) or "wave" (csrc/lz4w.hip, a
+wavefront per segment and every position searched); a container does not
+record which, and every reader reads both. The segmented container under it is
 ops/container.py, which MAFP10 (ops/fpcodec.py) and MAFB10 (ops/bytecodec.py)
 stand on as well, through the rank-plane codec they share (ops/rankcodec.py).
 
@@ -32,6 +35,12 @@ from .container import MIN_GAIN, OUT_STRIDE, SEG_SIZE, Workspace, effective_lens
 
 MAGIC = b"MALZ41"
 HEADER_FIXED = len(MAGIC) + 12  # magic + u64 raw_len + u32 n_seg
+LZ_PARSERS = ("lane", "wave")  # the device encoder's segment parser
+
+
+def check_lz_parser(lz_parser: str) -> None:
+    if lz_parser not in LZ_PARSERS:
+        raise ValueError(f'lz_parser is "lane" or "wave", got {lz_parser!r}')
 
 
 class Header(NamedTuple):
@@ -167,16 +176,20 @@ def decompress_buffer_cpu(blob: bytes) -> bytes:
 
 
 def compress_spans_gpu(
-    lib: Any, base: int, spans: Sequence[tuple[int, int]], ws: Workspace
+    lib: Any, base: int, spans: Sequence[tuple[int, int]], ws: Workspace,
+    lz_parser: str = "lane",
 ) -> list:
     """Containers of the device bytes ``(base + offset, raw_len)`` per span,
-    None where compression does not pay. One LZ4 launch per span, then
+    None where compression does not pay. One LZ4 launch per span, of the lane
+    encoder or with ``lz_parser`` "wave" of the wavefront encoder, then
     ``container.finish_containers``: one plan launch, ONE sync, one assemble
     launch and one D2H of the dense containers, all on the current stream."""
     import torch
 
+    check_lz_parser(lz_parser)
     if not spans:
         return []
+    launch = lib.ma_lz4_compress_wave if lz_parser == "wave" else lib.ma_lz4_compress
     stream = torch.cuda.current_stream().cuda_stream
     first_seg, n_segs, sb = [], [], 0
     for off, ln in spans:
@@ -184,7 +197,7 @@ def compress_spans_gpu(
         if sb + n_seg > ws.n_seg:
             raise RuntimeError("compress spans exceed the workspace")
         container.check(
-            lib.ma_lz4_compress(
+            launch(
                 base + off, ln, ws.stride.data_ptr() + sb * OUT_STRIDE,
                 ws.comp_lens.data_ptr() + sb * 4, OUT_STRIDE, n_seg, stream,
             ),
@@ -208,7 +221,8 @@ def compress_spans_gpu(
     )
 
 
-def compress_buffer_gpu(data: bytes) -> Optional[bytes]:
+def compress_buffer_gpu(data: bytes, lz_parser: str = "lane") -> Optional[bytes]:
+    check_lz_parser(lz_parser)
     if len(data) == 0:
         return None
     lib = load_lib(required=True)
@@ -216,15 +230,18 @@ def compress_buffer_gpu(data: bytes) -> Optional[bytes]:
 
     src = stage_to_gpu(data)
     ws = Workspace.for_lengths([len(data)], HEADER_FIXED)
-    return compress_spans_gpu(lib, src.data_ptr(), [(0, len(data))], ws)[0]
+    return compress_spans_gpu(lib, src.data_ptr(), [(0, len(data))], ws, lz_parser)[0]
 
 
-def compress_buffers_gpu(buffers: list, staged: "object" = None, only: "object" = None) -> list:
+def compress_buffers_gpu(
+    buffers: list, staged: "object" = None, only: "object" = None, lz_parser: str = "lane"
+) -> list:
     """Batched compression: ONE host->device transfer, ONE sync and ONE
     readback for a whole upload's blocks. ``staged`` is a
     ``stage_many_to_gpu`` result shared with the digest pass; ``only`` picks
     the buffers to compress. Returns per-buffer container bytes or None
     (incompressible / empty / not picked)."""
+    check_lz_parser(lz_parser)
     lib = load_lib(required=True)
     out: list = [None] * len(buffers)
     pick = sorted(set(range(len(buffers))) if only is None else set(only))
@@ -239,16 +256,19 @@ def compress_buffers_gpu(buffers: list, staged: "object" = None, only: "object" 
     src, src_offsets = staged
     spans = [(src_offsets[i], len(buffers[i])) for i in pick]
     ws = Workspace.for_lengths([n for _off, n in spans], HEADER_FIXED)
-    for i, container in zip(pick, compress_spans_gpu(lib, src.data_ptr(), spans, ws)):
+    for i, container in zip(pick, compress_spans_gpu(lib, src.data_ptr(), spans, ws, lz_parser)):
         out[i] = container
     return out
 
 
-def compress_buffers(buffers: list, staged: "object" = None, only: "object" = None) -> list:
+def compress_buffers(
+    buffers: list, staged: "object" = None, only: "object" = None, lz_parser: str = "lane"
+) -> list:
     """GPU-batched when present; None entries otherwise (CPU compression
     is not worth its cost on the storage path)."""
+    check_lz_parser(lz_parser)
     if gpu_available():
-        return compress_buffers_gpu(buffers, staged=staged, only=only)
+        return compress_buffers_gpu(buffers, staged=staged, only=only, lz_parser=lz_parser)
     return [None] * len(buffers)
 
 
@@ -290,11 +310,13 @@ def decompress_buffer_gpu(blob: bytes) -> bytes:
 # ---------------------------------------------------------------------------
 
 
-def compress_buffer(data: bytes) -> Optional[bytes]:
+def compress_buffer(data: bytes, lz_parser: str = "lane") -> Optional[bytes]:
     """GPU when present; else the native C++ segment-parallel codec (the
-    pure-Python fallback alone was not worth its cost — the C++ one is)."""
+    pure-Python fallback alone was not worth its cost — the C++ one is).
+    ``lz_parser`` picks the device encoder's parser; the host codec has one."""
+    check_lz_parser(lz_parser)
     if gpu_available():
-        return compress_buffer_gpu(data)
+        return compress_buffer_gpu(data, lz_parser)
     core = _native_core()
     if core is not None:
         return core.malz_compress(bytes(data), MIN_GAIN)

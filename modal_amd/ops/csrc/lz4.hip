@@ -11,7 +11,9 @@
 //
 // Format per segment: standard LZ4 block (token | literals | 2B LE offset |
 // extended lengths), interoperable with any LZ4 block decoder; the container
-// framing (segment table) lives host-side in ops/compress.py.
+// framing (segment table) lives host-side in ops/compress.py. Its sibling
+// lz4w.hip encodes the same segments with a wavefront each and a search of
+// every position (lz_parser="wave"); this file decodes both.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>

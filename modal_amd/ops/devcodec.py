@@ -194,7 +194,7 @@ def _check_block_size(block_size: int) -> None:
 def _encode_window(
     lib: Any, sc: Workspace, ptr: int, spans: Sequence[tuple[int, int]],
     digests: list, known: Optional[Callable[[str], bool]], elem_size: int = 0,
-    rank_coding: str = "fixed",
+    rank_coding: str = "fixed", lz_parser: str = "lane",
 ) -> list[EncodedBlock]:
     """Blocks of one window (<= WINDOW source bytes) of the object at ptr.
     ``digests`` holds the short blocks' digests; full blocks are None. With
@@ -206,14 +206,15 @@ def _encode_window(
     first and each block goes through the codec of the element size the probe
     found (1, 2 or 4; a short block only at 1), or stays raw where it found
     none. ``rank_coding`` "rice" puts MARC10 where MAFP10 and MAFB10 stand and
-    its estimate into the probe; nothing else changes."""
+    its estimate into the probe; ``lz_parser`` "wave" has the LZ4 pass run the
+    wavefront encoder (csrc/lz4w.hip); nothing else changes."""
     tree = [i for i, d in enumerate(digests) if d is None]
     for i, d in zip(tree, _tree_digests(lib, ptr, [spans[i] for i in tree])):
         digests[i] = d
     skip = [known is not None and known(d) for d in digests]
     cand = [i for i, (_o, ln) in enumerate(spans) if ln >= COMPRESS_MIN and not skip[i]]
     containers = dict(
-        zip(cand, compress.compress_spans_gpu(lib, ptr, [spans[i] for i in cand], sc))
+        zip(cand, compress.compress_spans_gpu(lib, ptr, [spans[i] for i in cand], sc, lz_parser))
     )
     left = [i for i in cand if containers[i] is None] if elem_size else []
     if elem_size in (1, fpcodec.AUTO):
@@ -259,6 +260,7 @@ def iter_encode_device(
     objects: Sequence[tuple[int, int]], *, block_size: int = BLOCK_SIZE,
     known: Optional[Callable[[str], bool]] = None,
     elem_sizes: Optional[Sequence[int]] = None, rank_coding: str = "fixed",
+    lz_parser: str = "lane",
 ) -> Iterator[tuple[int, EncodedBlock]]:
     """Encode several device objects ``(ptr, nbytes)``; yields
     ``(object index, block)`` in object then block order, a window at a time,
@@ -274,9 +276,13 @@ def iter_encode_device(
     bytes finds, at the element size, 1, 2 or 4, it finds (per block; none:
     raw), 0 does not; digests are of the RAW block either way.
     ``rank_coding`` "rice" has those codecs write Rice-coded MARC10 containers
-    (ops/ricecodec.py) where "fixed", the default, writes MAFP10 and MAFB10."""
+    (ops/ricecodec.py) where "fixed", the default, writes MAFP10 and MAFB10.
+    ``lz_parser`` "wave" has the LZ4 pass parse every segment with a wavefront
+    (csrc/lz4w.hip) where "lane", the default, gives it a lane; both write
+    MALZ41."""
     _check_block_size(block_size)
     _check_rank_coding(rank_coding)
+    compress.check_lz_parser(lz_parser)
     if elem_sizes is None:
         elem_sizes = [0] * len(objects)
     if len(elem_sizes) != len(objects) or any(es not in _ELEM_SIZES for es in elem_sizes):
@@ -307,7 +313,8 @@ def iter_encode_device(
                 else:
                     digests = [short.get((oi, w0 + k)) for k in range(len(wspans))]
                     blocks = _encode_window(
-                        lib, sc, ptr, wspans, digests, known, elem_sizes[oi], rank_coding
+                        lib, sc, ptr, wspans, digests, known, elem_sizes[oi], rank_coding,
+                        lz_parser,
                     )
             for blk in blocks:
                 yield oi, blk
@@ -315,11 +322,12 @@ def iter_encode_device(
 
 def encode_device(
     ptr: int, nbytes: int, *, block_size: int = BLOCK_SIZE, elem_size: int = 0,
-    rank_coding: str = "fixed",
+    rank_coding: str = "fixed", lz_parser: str = "lane",
 ) -> list[EncodedBlock]:
     """CAS blocks of the ``nbytes`` at device pointer ``ptr``."""
     it = iter_encode_device(
-        [(ptr, nbytes)], block_size=block_size, elem_sizes=[elem_size], rank_coding=rank_coding
+        [(ptr, nbytes)], block_size=block_size, elem_sizes=[elem_size], rank_coding=rank_coding,
+        lz_parser=lz_parser,
     )
     return [blk for _oi, blk in it]
 
@@ -331,13 +339,15 @@ def _tensor_span(t: Any) -> tuple[int, int]:
 
 
 def encode_tensor(
-    t: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0, rank_coding: str = "fixed"
+    t: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0, rank_coding: str = "fixed",
+    lz_parser: str = "lane",
 ) -> list[EncodedBlock]:
     """``elem_size`` is the caller's to give: it is not inferred from t's
     dtype (``fpcodec.AUTO`` infers it from the bytes)."""
     ptr, nbytes = _tensor_span(t)
     return encode_device(
-        ptr, nbytes, block_size=block_size, elem_size=elem_size, rank_coding=rank_coding
+        ptr, nbytes, block_size=block_size, elem_size=elem_size, rank_coding=rank_coding,
+        lz_parser=lz_parser,
     )
 
 
@@ -429,13 +439,17 @@ def decode_tensor(blocks: Sequence, t: Any, *, verify: bool = True) -> None:
 
 
 def encode_host(
-    data: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0, rank_coding: str = "fixed"
+    data: Any, *, block_size: int = BLOCK_SIZE, elem_size: int = 0, rank_coding: str = "fixed",
+    lz_parser: str = "lane",
 ) -> list[EncodedBlock]:
     """Same manifest from host bytes (CPU tensors, CPU-only processes).
     ``fpcodec.AUTO`` runs the probe's numpy twin (ops/probe.py: element sizes
-    1, 2 and 4) on every block LZ4 declined or was too short for."""
+    1, 2 and 4) on every block LZ4 declined or was too short for.
+    ``lz_parser`` reaches the device encoder where ``compress_buffer`` finds a
+    GPU; the host encoder has one parser."""
     _check_block_size(block_size)
     _check_rank_coding(rank_coding)
+    compress.check_lz_parser(lz_parser)
     if elem_size not in _ELEM_SIZES:
         raise ValueError("elem_size is one of 0, 1, 2, 4, fpcodec.AUTO")
     from .compress import compress_buffer
@@ -444,7 +458,7 @@ def encode_host(
     blocks = []
     for off, ln in _spans(len(view), block_size):
         block = bytes(view[off : off + ln])
-        z = compress_buffer(block) if ln >= COMPRESS_MIN else None
+        z = compress_buffer(block, lz_parser) if ln >= COMPRESS_MIN else None
         es = elem_size
         if z is None and es == fpcodec.AUTO and ln >= BYTE_MIN:
             es = probe.choose_elem_size(

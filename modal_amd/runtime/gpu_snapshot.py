@@ -309,7 +309,9 @@ def restore_payload(data: bytes, store: Any = None) -> dict:
 _RESTORE_CHUNK_BLOCKS = 8
 
 
-def capture_manifest(store: Any, float_codec: Any = False, rank_coding: str = "fixed") -> bytes:
+def capture_manifest(
+    store: Any, float_codec: Any = False, rank_coding: str = "fixed", lz_parser: str = "lane"
+) -> bytes:
     """Block-addressed snapshot: every registered tensor and tracked raw
     allocation is cut into CAS blocks, hashed and compressed where it lives
     (CUDA memory on the GPU through ops/devcodec.py, CPU tensors on the
@@ -331,13 +333,18 @@ def capture_manifest(store: Any, float_codec: Any = False, rank_coding: str = "f
 
     ``rank_coding`` "rice" has those codecs Rice-code the ranks (MARC10,
     ops/ricecodec.py) where "fixed", the default, packs them at a fixed width
-    (MAFP10, MAFB10): smaller containers from slower coding kernels."""
-    from ..ops import devcodec, fpcodec, rawmem
+    (MAFP10, MAFB10): smaller containers from slower coding kernels.
+
+    ``lz_parser`` "wave" has the LZ4 pass on the device parse every segment
+    with a wavefront that searches every position (ops/csrc/lz4w.hip) where
+    "lane", the default, gives a segment one lane; both write MALZ41."""
+    from ..ops import compress, devcodec, fpcodec, rawmem
 
     if float_codec not in (False, True, "auto"):
         raise ValueError(f'float_codec is False, True or "auto", got {float_codec!r}')
     if rank_coding not in ("fixed", "rice"):
         raise ValueError(f'rank_coding is "fixed" or "rice", got {rank_coding!r}')
+    compress.check_lz_parser(lz_parser)
     untyped = fpcodec.AUTO if float_codec == "auto" else 0
 
     def hint(t: Any) -> int:
@@ -376,7 +383,9 @@ def capture_manifest(store: Any, float_codec: Any = False, rank_coding: str = "f
             else:
                 # byte-level view: numpy() would reject bf16/fp8 dtypes
                 flat = src.reshape(-1).view(torch.uint8).numpy()
-                for blk in devcodec.encode_host(flat, elem_size=hint(t), rank_coding=rank_coding):
+                for blk in devcodec.encode_host(
+                    flat, elem_size=hint(t), rank_coding=rank_coding, lz_parser=lz_parser
+                ):
                     add(entry, blk)
     lib = rawmem.load_lib()
     if lib is not None:
@@ -391,7 +400,8 @@ def capture_manifest(store: Any, float_codec: Any = False, rank_coding: str = "f
         objects = [(ptr, nbytes) for _e, ptr, nbytes, _es, _k in on_device]
         hints = [es for _e, _ptr, _n, es, _k in on_device]
         for oi, blk in devcodec.iter_encode_device(
-            objects, known=store.has, elem_sizes=hints, rank_coding=rank_coding
+            objects, known=store.has, elem_sizes=hints, rank_coding=rank_coding,
+            lz_parser=lz_parser,
         ):
             add(on_device[oi][0], blk)
     payload = {

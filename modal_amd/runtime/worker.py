@@ -195,13 +195,16 @@ class WorkerRPCTarget:
 
         return await asyncio.get_running_loop().run_in_executor(None, capture_payload)
 
-    async def snapshot_manifest(self, float_codec: Any = False, rank_coding: str = "fixed") -> bytes:
+    async def snapshot_manifest(
+        self, float_codec: Any = False, rank_coding: str = "fixed", lz_parser: str = "lane"
+    ) -> bytes:
         """Block-addressed snapshot (gpu_snapshot.capture_manifest): the
         state's blocks go straight into the shared CAS, encoded on the GPU
         where they live; only the small manifest crosses the socket.
         ``float_codec`` True offers float tensors to the float-plane codec,
         ``"auto"`` also untyped tensors and tracked raw allocations;
-        ``rank_coding`` "rice" has that codec write MARC10 containers."""
+        ``rank_coding`` "rice" has that codec write MARC10 containers;
+        ``lz_parser`` "wave" has the LZ4 pass run the wavefront encoder."""
         from ..exception import InvalidError
         from .gpu_snapshot import capture_manifest
 
@@ -209,8 +212,11 @@ class WorkerRPCTarget:
             raise InvalidError(f'float_codec is False, True or "auto", got {float_codec!r}')
         if rank_coding not in ("fixed", "rice"):
             raise InvalidError(f'rank_coding is "fixed" or "rice", got {rank_coding!r}')
+        if lz_parser not in ("lane", "wave"):
+            raise InvalidError(f'lz_parser is "lane" or "wave", got {lz_parser!r}')
         return await asyncio.get_running_loop().run_in_executor(
-            None, capture_manifest, self._runtime.blob_store, float_codec, rank_coding
+            None, capture_manifest, self._runtime.blob_store, float_codec, rank_coding,
+            lz_parser,
         )
 
 

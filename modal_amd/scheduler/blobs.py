@@ -32,9 +32,20 @@ def _hash_bytes(data: Union[bytes, memoryview]) -> str:
 
 
 class BlobStore:
-    """CAS on the local filesystem: blobs/<aa>/<sha256>."""
+    """CAS on the local filesystem: blobs/<aa>/<sha256>.
 
-    def __init__(self, root: str):
+    ``lz_parser`` "wave" has the serial ``put`` / ``put_many`` compress calls
+    run the wavefront LZ4 encoder (ops/csrc/lz4w.hip) where "lane", the
+    default, runs the lane encoder; the stored containers are MALZ41 either
+    way. The pipelined upload path (ops/pipeline.py) keeps the lane encoder:
+    handing it the option is a follow-up."""
+
+    def __init__(self, root: str, lz_parser: str = "lane"):
+        from ..ops.compress import check_lz_parser
+
+        check_lz_parser(lz_parser)
+        # what the compress calls get on top of their defaults
+        self._lz_options = {} if lz_parser == "lane" else {"lz_parser": lz_parser}
         self.root = root
         os.makedirs(root, exist_ok=True)
 
@@ -59,7 +70,7 @@ class BlobStore:
             try:
                 from ..ops.compress import compress_buffer
 
-                z = compress_buffer(payload)
+                z = compress_buffer(payload, **self._lz_options)
                 if z is not None:
                     payload = z
                     compressed = True
@@ -114,10 +125,13 @@ class BlobStore:
                 from ..ops.compress import compress_buffers
 
                 if staged is not None:
-                    payloads = compress_buffers(buffers, staged=staged, only=todo)
+                    payloads = compress_buffers(
+                        buffers, staged=staged, only=todo, **self._lz_options
+                    )
                 else:
                     payloads = [None] * len(buffers)
-                    for i, payload in zip(todo, compress_buffers([buffers[i] for i in todo])):
+                    picked = compress_buffers([buffers[i] for i in todo], **self._lz_options)
+                    for i, payload in zip(todo, picked):
                         payloads[i] = payload
                 for i in todo:
                     if payloads[i] is not None:

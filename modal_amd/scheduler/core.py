@@ -1389,7 +1389,7 @@ class Scheduler:
     # -- worker GPU snapshots ---------------------------------------------
     async def worker_snapshot(
         self, worker_id: int, block_addressed: bool = False, float_codec: Any = False,
-        rank_coding: str = "fixed",
+        rank_coding: str = "fixed", lz_parser: str = "lane",
     ) -> dict:
         """Capture a worker's snapshot-visible GPU state (registered
         tensors + tracked raw hipMalloc allocations + RNG) into the CAS.
@@ -1408,7 +1408,10 @@ class Scheduler:
 
         rank_coding="rice" (needs float_codec): those blocks are stored as
         Rice-coded MARC10 containers (ops/ricecodec.py), a few points of raw
-        smaller; restore reads every format."""
+        smaller; restore reads every format.
+
+        lz_parser="wave" (needs block_addressed): the LZ4 pass on the device
+        runs the wavefront encoder (ops/csrc/lz4w.hip); same MALZ41."""
         if float_codec not in (False, True, "auto"):
             raise InvalidError(f'float_codec is False, True or "auto", got {float_codec!r}')
         if float_codec and not block_addressed:
@@ -1417,14 +1420,20 @@ class Scheduler:
             raise InvalidError(f'rank_coding is "fixed" or "rice", got {rank_coding!r}')
         if rank_coding == "rice" and not float_codec:
             raise InvalidError('rank_coding="rice" needs float_codec')
+        if lz_parser not in ("lane", "wave"):
+            raise InvalidError(f'lz_parser is "lane" or "wave", got {lz_parser!r}')
+        if lz_parser != "lane" and not block_addressed:
+            raise InvalidError("lz_parser needs block_addressed=True")
         w = self.pool.workers.get(int(worker_id))
         if w is None:
             raise NotFoundError(f"worker {worker_id} not connected")
         rpc = "snapshot_manifest" if block_addressed else "snapshot_state"
-        params = {"float_codec": float_codec} if float_codec else None
+        params = {"float_codec": float_codec} if float_codec else {}
         if rank_coding != "fixed":
             params["rank_coding"] = rank_coding
-        data = await w.conn.call(rpc, params, timeout=300)
+        if lz_parser != "lane":
+            params["lz_parser"] = lz_parser
+        data = await w.conn.call(rpc, params or None, timeout=300)
         blob_id = self.blob_store.put(data)
         return {"snapshot_id": blob_id}
 

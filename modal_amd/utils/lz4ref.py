@@ -7,6 +7,8 @@ CAS entries on GPU-less machines. Not fast — the GPU kernel is the hot path.
 ``compress_block`` is an exact model of the kernel's ``lz4_compress_segment``
 (same 7-bit hash, same skip through miss runs, same emit order, same slot
 bail-out), so a test can hold every byte the kernel emits to it.
+``compress_block_wave`` is the same for the wavefront encoder,
+ops/csrc/lz4w.hip, which looks at every position of the segment.
 ``decompress_block`` bounds every read and raises ``ValueError`` on anything
 the kernel's ``lz4_decompress_segment`` rejects.
 """
@@ -19,6 +21,7 @@ MIN_MATCH = 4
 MFLIMIT = 12
 LASTLITERALS = 5
 HASH_BITS = 7
+WAVE_HASH_BITS = 12
 
 
 def _hash(v: int) -> int:
@@ -89,6 +92,52 @@ def compress_block(src: bytes, accel: bool = True, max_out: Optional[int] = None
     if lit >= 15:
         out += _ext_len(lit)
     out += src[anchor:]
+    return bytes(out)
+
+
+def compress_block_wave(src: bytes, max_out: Optional[int] = None) -> bytes:
+    """The parse of the wavefront encoder (ops/csrc/lz4w.hip), byte for byte:
+    a 12-bit hash, every position below ``n - MFLIMIT`` looked up and then
+    inserted (none skipped, so the candidate of a position is the latest
+    earlier one with its hash), greedy selection, the lane encoder's encoding.
+    ``b""`` where the block is longer than the slot ``max_out``."""
+    n = len(src)
+    mflimit = n - MFLIMIT
+    table: dict[int, int] = {}
+    cand = []
+    for p in range(max(mflimit, 0)):
+        v = int.from_bytes(src[p : p + 4], "little")
+        h = ((v * 2654435761) & 0xFFFFFFFF) >> (32 - WAVE_HASH_BITS)
+        cand.append(table.get(h, -1))
+        table[h] = p
+    out = bytearray()
+    ip = anchor = 0
+    while ip < mflimit:
+        q = cand[ip]
+        if q < 0 or src[q : q + 4] != src[ip : ip + 4]:
+            ip += 1
+            continue
+        mlen = MIN_MATCH
+        maxm = n - LASTLITERALS - ip
+        while mlen < maxm and src[q + mlen] == src[ip + mlen]:
+            mlen += 1
+        lit, ml = ip - anchor, mlen - MIN_MATCH
+        out.append((min(lit, 15) << 4) | min(ml, 15))
+        if lit >= 15:
+            out += _ext_len(lit)
+        out += src[anchor:ip]
+        out += (ip - q).to_bytes(2, "little")
+        if ml >= 15:
+            out += _ext_len(ml)
+        ip += mlen
+        anchor = ip
+    lit = n - anchor
+    out.append(min(lit, 15) << 4)
+    if lit >= 15:
+        out += _ext_len(lit)
+    out += src[anchor:]
+    if max_out is not None and len(out) > max_out:
+        return b""
     return bytes(out)
 
 
