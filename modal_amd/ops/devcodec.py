@@ -43,7 +43,9 @@ import numpy as np
 from ..scheduler.blobs import BLOCK_SIZE, BlobStore
 from . import bytecodec, compress, fpcodec, load_lib, probe, ricecodec
 from .container import SEG_SIZE, Workspace
-from .hashing import GPU_MIN_BYTES, content_digest, leaf_table, sha256_leaves_gpu, tree_roots
+from .hashing import (
+    GPU_MIN_BYTES, launch_digests, content_digest, leaf_table, sha256_leaves_gpu, tree_roots,
+)
 from .staging import copy_from_device, copy_to_device
 
 WINDOW = 64 * 1024 * 1024  # source bytes encoded per plan/assemble round
@@ -52,6 +54,13 @@ COMPRESS_MIN = BlobStore.COMPRESS_MIN
 # the e8m0 scale tensor of an MX-quantised weight is 1/32 of it and rarely
 # reaches COMPRESS_MIN, and it is what the codec shrinks most.
 BYTE_MIN = 64 * 1024
+# A short block's plain SHA-256 goes to the wavefront kernel (csrc/sha256w.hip)
+# from this size and to a lane of sha256_many_kernel below it: the smallest
+# length measured (profiles/README.md, "Wavefront tail hash") from which the
+# wavefront kernel's slowest launch beat the lane kernel's fastest, which is
+# the kernel's own batch, 4 KiB (131 us against 200 us; 0.25 s against 0.41 s
+# at 8 MiB - 1). Below one batch there is nothing to take off the chain.
+LONG_MIN = 4096
 RUN_MAX_BLOCKS = 128  # decode: blocks per decompress launch, at most
 _ELEM_SIZES = (0, 1, *fpcodec.ELEM_SIZES, fpcodec.AUTO)  # what an element size hint may be
 _RANK_CODINGS = ("fixed", "rice")  # how a rank-plane codec codes the ranks
@@ -93,7 +102,9 @@ def release_scratch() -> None:
 
 def _short_digests(lib: Any, items: Sequence[tuple[int, int]]) -> list[str]:
     """Plain SHA-256 of many (absolute pointer, length) messages in ONE
-    dispatch, one message per lane."""
+    dispatch: a wavefront per message of LONG_MIN bytes and more
+    (ma_sha256_long), a lane per shorter one (ma_sha256_many), both launched
+    before either is waited for."""
     if not items:
         return []
     base = min(p for p, _n in items)
@@ -103,7 +114,13 @@ def _short_digests(lib: Any, items: Sequence[tuple[int, int]]) -> list[str]:
 
     torch.cuda.current_stream().synchronize()
     t0 = time.perf_counter()
-    dig = sha256_leaves_gpu(lib, base, offsets, lengths)
+    dig = np.empty((len(items), 32), dtype=np.uint8)
+    parts = []
+    for entry, which in ((lib.ma_sha256_long, lengths >= LONG_MIN), (lib.ma_sha256_many, lengths < LONG_MIN)):
+        if which.any():
+            parts.append((which, launch_digests(entry, base, offsets[which], lengths[which])))
+    for which, out in parts:
+        dig[which] = out.cpu().numpy()
     dt = time.perf_counter() - t0
     if dt > last_stats["tail_hash_s"]:
         last_stats["tail_hash_s"] = dt
@@ -124,8 +141,8 @@ def _tree_digests(lib: Any, ptr: int, spans: Sequence[tuple[int, int]]) -> list[
 def verify_device(objects: Sequence[tuple[int, Sequence[tuple[str, int]]]]) -> None:
     """Re-hash decoded device memory against its manifest. ``objects`` is
     ``[(ptr, [(digest, raw_len), ...])]``, the blocks of each object in
-    order. Every short block of the call shares ONE dispatch (a single lane
-    takes ~0.5 s for a message just under 8 MiB, so a restore verifies all
+    order. Every short block of the call shares ONE dispatch (a message just
+    under 8 MiB is one serial chain of ~0.2 s, so a restore verifies all
     its objects in one call); full blocks hash a few blocks' leaves at a time.
     Raises ``ValueError("snapshot block <i> digest mismatch")``."""
     lib = load_lib(required=True)

@@ -29,6 +29,7 @@ from . import gpu_available, load_lib
 LEAF_SIZE = 8 * 1024
 TREE_DOMAIN = b"modal-amd-tree-v1"
 GPU_MIN_BYTES = 8 * 1024 * 1024  # below this, CPU wins (kernel+copy overhead)
+LONG_BATCH = 4096  # bytes sha256_long_kernel (csrc/sha256w.hip) prepares at a time
 
 Buffer = Union[bytes, bytearray, memoryview]
 
@@ -82,22 +83,36 @@ def tree_roots(spans: Sequence[tuple[int, int]], counts: Any, leaf_digests: byte
     return roots
 
 
-def sha256_leaves_gpu(lib: Any, base: int, offsets: Any, lengths: Any) -> Any:
-    """One ma_sha256_many over (base + offsets[i], lengths[i]), numpy int64
-    tables, on the current stream; [n, 32] uint8 on the host."""
+def launch_digests(entry: Any, base: int, offsets: Any, lengths: Any) -> Any:
+    """Launch ``entry`` (ma_sha256_many or ma_sha256_long) over the messages
+    (base + offsets[i], lengths[i]) on the current stream; [n, 32] uint8 on
+    the device, not waited for."""
     import torch
 
     n = len(offsets)
     off_d = torch.from_numpy(offsets).cuda()
     len_d = torch.from_numpy(lengths).cuda()
     out = torch.empty((n, 32), dtype=torch.uint8, device="cuda")
-    rc = lib.ma_sha256_many(
+    rc = entry(
         base, off_d.data_ptr(), len_d.data_ptr(), out.data_ptr(), n,
         torch.cuda.current_stream().cuda_stream,
     )
     if rc != 0:
         raise RuntimeError(f"sha256 kernel failed: hipError {rc}")
-    return out.cpu().numpy()
+    return out
+
+
+def sha256_leaves_gpu(lib: Any, base: int, offsets: Any, lengths: Any) -> Any:
+    """One ma_sha256_many over (base + offsets[i], lengths[i]), numpy int64
+    tables, on the current stream; [n, 32] uint8 on the host."""
+    return launch_digests(lib.ma_sha256_many, base, offsets, lengths).cpu().numpy()
+
+
+def sha256_long_gpu(lib: Any, base: int, offsets: Any, lengths: Any) -> Any:
+    """One ma_sha256_long over the same tables: a wavefront per message where
+    sha256_leaves_gpu gives it a lane, for messages long enough to be felt as
+    one serial chain (devcodec.LONG_MIN). Same digests, same contract."""
+    return launch_digests(lib.ma_sha256_long, base, offsets, lengths).cpu().numpy()
 
 
 def _tree_sha256_gpu(data: Buffer) -> Optional[bytes]:
