@@ -75,8 +75,8 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
                 ctypes.c_void_p,
             ]
             ptr, i32 = ctypes.c_void_p, ctypes.c_int
-            lib.ma_fpz_rank.restype = ctypes.c_int
-            lib.ma_fpz_rank.argtypes = [ptr] * 3 + [i32] + [ptr] * 3 + [i32, ptr]
+            lib.ma_rank_hist.restype = ctypes.c_int
+            lib.ma_rank_hist.argtypes = [ptr] * 3 + [i32] + [ptr] * 3 + [i32, ptr]
             lib.ma_fpz_probe.restype = ctypes.c_int
             lib.ma_fpz_probe.argtypes = [ptr] * 4 + [i32, ptr]
             lib.ma_rank_probe.restype = ctypes.c_int
@@ -93,8 +93,6 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
             )
             lib.ma_fpz_decode.restype = ctypes.c_int
             lib.ma_fpz_decode.argtypes = [ptr] * 10 + [i32, ptr]
-            lib.ma_bytez_rank.restype = ctypes.c_int
-            lib.ma_bytez_rank.argtypes = [ptr] * 6 + [i32, ptr]
             lib.ma_bytez_encode.restype = ctypes.c_int
             lib.ma_bytez_encode.argtypes = (
                 [ptr] * 6 + [i32, ptr, i32, ctypes.c_long, ptr]

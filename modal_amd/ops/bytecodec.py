@@ -53,7 +53,7 @@ from .rankcodec import HEADER_FIXED, Header  # noqa: F401  (public names)
 
 MAGIC = b"MAFB10"
 FORMAT = rankcodec.Format(
-    MAGIC, (1,), "1", "bytez", "ma_bytez_rank", "ma_bytez_encode", "ma_bytez_decode",
+    MAGIC, (1,), "1", "bytez", "ma_bytez_encode", "ma_bytez_decode",
     es_in_abi=False,
 )
 

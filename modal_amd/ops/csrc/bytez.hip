@@ -6,9 +6,9 @@
 // frequency order, at a bit width chosen per 4 KiB segment, the rare ranks
 // escaped. It is for fp8 tensors, fp8 KV caches and e8m0 scale tensors.
 //
-//   hist      per block: LDS histogram of all its bytes, one global merge
-//   rank      fpz_rank_kernel (fpz.hip), through ma_fpz_rank_counts
-//   encode    one wavefront per segment -> its stride slot + comp_lens
+//   hist,     rankhist.hip (ma_rank_hist at es = 1): the histogram of all a
+//   rank      block's bytes and its rank tables
+//   encode   one wavefront per segment -> its stride slot + comp_lens
 //   assemble  rank_assemble_kernel (fpz.hip), given this magic and es = 1
 //   decode    one wavefront per segment of a run of containers
 //
@@ -59,10 +59,6 @@
 #include "malz_common.h"
 #include "rank_common.h"
 
-#define BZ_HIST_BLOCK 256
-#define BZ_HIST_GROUPS 64
-#define BZ_HIST_COPIES 16
-#define BZ_HIST_UNROLL 4  // 16-byte loads a lane has in flight
 #define BZ_RUN_DWORDS 16  // a lane's run is at most 64 bytes
 // 4096 bytes, a pad dword per 16, and the two dwords an unaligned 8-byte read
 // of the last code bytes may touch behind them
@@ -88,73 +84,6 @@ __device__ __forceinline__ void stage_at_zero(const uint8_t* __restrict__ src, i
     if (lane == WAVE - 1) w1 = (mis && k + 1 < n_src) ? s1[k + 1] : 0u;
     if (k < n_out) in32[padw(k)] = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
   }
-}
-
-// ---------------------------------------------------------------------------
-// histogram of every byte of a block
-// ---------------------------------------------------------------------------
-//
-// Loads as in fpz_probe_kernel: aligned 16-byte chunks from the chunk the
-// span's first byte lives in; only the first and the last chunk can hold
-// bytes outside the span and take the per-byte check. LDS as there too:
-// bins[bin][copy], copy = lane % 16, so the bank depends on the lane and
-// hardly on the data. fp8 Gaussians put a fifth of the bytes on four bins.
-
-__device__ __forceinline__ void bz_count(const uint4 v, int64_t q, int mis16, int64_t n,
-                                         uint32_t* mine) {
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  const int64_t i0 = 16 * q - mis16;  // span offset of the chunk's first byte
-  if (i0 >= 0 && i0 + 16 <= n) {
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        atomicAdd(mine + ((w[d] >> (8 * k)) & 255u) * BZ_HIST_COPIES, 1u);
-  } else {  // the span's first or last chunk: count only its own bytes
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int64_t i = i0 + 4 * d + k;
-        if (i >= 0 && i < n) atomicAdd(mine + ((w[d] >> (8 * k)) & 255u) * BZ_HIST_COPIES, 1u);
-      }
-  }
-}
-
-extern "C" __global__ __launch_bounds__(BZ_HIST_BLOCK) void bytez_hist_kernel(
-    const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_src_off,
-    const int64_t* __restrict__ blk_raw_len, uint32_t* __restrict__ counts, int blk_base) {
-  __shared__ uint32_t bins[256 * BZ_HIST_COPIES];
-  const int b = blk_base + blockIdx.y;
-  const int tid = threadIdx.x;
-  const int64_t n = blk_raw_len[b];
-  if (n <= 0) return;
-  const uint8_t* first = src + blk_src_off[b];
-  const int mis16 = (int)(reinterpret_cast<uintptr_t>(first) & 15);
-  const int64_t n_chunks = (mis16 + n + 15) >> 4;  // the last one holds byte n - 1
-  if ((int64_t)blockIdx.x * BZ_HIST_BLOCK >= n_chunks) return;  // nothing here: no merge either
-
-  uint4* z = reinterpret_cast<uint4*>(bins);
-  for (int k = tid; k < 256 * BZ_HIST_COPIES / 4; k += BZ_HIST_BLOCK) z[k] = make_uint4(0, 0, 0, 0);
-  __syncthreads();
-
-  const uint4* chunks = reinterpret_cast<const uint4*>(first - mis16);
-  uint32_t* mine = &bins[tid & (BZ_HIST_COPIES - 1)];
-  const int64_t step = (int64_t)gridDim.x * BZ_HIST_BLOCK;
-  int64_t q = (int64_t)blockIdx.x * BZ_HIST_BLOCK + tid;
-  for (; q + (BZ_HIST_UNROLL - 1) * step < n_chunks; q += BZ_HIST_UNROLL * step) {
-    uint4 v[BZ_HIST_UNROLL];
-#pragma unroll
-    for (int u = 0; u < BZ_HIST_UNROLL; ++u) v[u] = chunks[q + u * step];
-#pragma unroll
-    for (int u = 0; u < BZ_HIST_UNROLL; ++u) bz_count(v[u], q + u * step, mis16, n, mine);
-  }
-  for (; q < n_chunks; q += step) bz_count(chunks[q], q, mis16, n, mine);
-  __syncthreads();
-  uint32_t total = 0;
-  for (int k = 0; k < BZ_HIST_COPIES; ++k)  // rotated by the thread: off one bank
-    total += bins[tid * BZ_HIST_COPIES + ((k + tid) & (BZ_HIST_COPIES - 1))];
-  if (total) atomicAdd(&counts[(int64_t)b * 256 + tid], total);
 }
 
 // ---------------------------------------------------------------------------
@@ -428,20 +357,6 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
 // ---------------------------------------------------------------------------
 // host entry points
 // ---------------------------------------------------------------------------
-
-// counts (n_blocks x 256 u32) must come in zeroed.
-extern "C" int ma_bytez_rank(const void* src, const void* blk_src_off, const void* blk_raw_len,
-                             void* counts, void* order, void* rank_of, int n_blocks,
-                             void* stream) {
-  if (n_blocks <= 0) return 0;
-  const int rc = launch_chunked(n_blocks, [&](int base, int ny) {
-    hipLaunchKernelGGL(bytez_hist_kernel, dim3(BZ_HIST_GROUPS, ny), dim3(BZ_HIST_BLOCK), 0,
-                       (hipStream_t)stream, (const uint8_t*)src,
-                       (const int64_t*)blk_src_off, (const int64_t*)blk_raw_len,
-                       (uint32_t*)counts, base);
-  });
-  return rc ? rc : ma_fpz_rank_counts(counts, order, rank_of, n_blocks, stream);
-}
 
 // max_segs: the largest segment count of any block (bounds the grid).
 extern "C" int ma_bytez_encode(const void* src, const void* blk_src_off,

@@ -1,5 +1,5 @@
 // Shared by the rank codecs (fpz.hip, bytez.hip, ricez.hip) for gfx950: the size of the
-// header their containers have, the rank pass of fpz.hip that both use, how a
+// header their containers have, how a
 // segment's elements are split among the lanes of its wavefront, wavefront
 // sums and scans, and the copy of a decoded segment from LDS to any
 // destination.
@@ -9,10 +9,6 @@
 #include "malz_common.h"
 
 #define RANK_HEADER_FIXED 276  // magic 6, raw_len 8, es 1, reserved 1, n_seg 4, order 256
-
-// fpz.hip: the rank tables of histograms the caller already has.
-extern "C" int ma_fpz_rank_counts(const void* counts, void* order, void* rank_of, int n_blocks,
-                                  void* stream);
 
 // Staging of fpz.hip and ricez.hip (the comment at the top of fpz.hip):
 // mis (<= 3) + 4096 bytes, rounded up to dwords, plus a pad dword per 16

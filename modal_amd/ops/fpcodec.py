@@ -58,7 +58,7 @@ from .rankcodec import HEADER_FIXED, Header, block_order  # noqa: F401  (public 
 MAGIC = b"MAFP10"
 ELEM_SIZES = (2, 4)
 FORMAT = rankcodec.Format(
-    MAGIC, ELEM_SIZES, "2 or 4", "fpz", "ma_fpz_rank", "ma_fpz_encode", "ma_fpz_decode",
+    MAGIC, ELEM_SIZES, "2 or 4", "fpz", "ma_fpz_encode", "ma_fpz_decode",
     es_in_abi=True,
 )
 
@@ -86,7 +86,7 @@ AUTO = -1
 def probe_counts_cpu(data: Any) -> tuple[Any, Any]:
     """(counts2, counts4): the histograms ``block_order`` sorts at ``es`` 2
     and at ``es`` 4, 256 int64 counts each. The numpy twin of
-    ``fpz_probe_kernel``."""
+    ``ma_fpz_probe``."""
     data = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
     n = len(data)
     return (

@@ -5,7 +5,7 @@ MAFB10 (ops/bytecodec.py) codes every byte of a block, MAFP10 (ops/fpcodec.py)
 the top byte of every 2- or 4-byte element. A caller that has no element type
 (a tracked raw allocation, a uint8 tensor of packed fp8) asks the bytes: the
 probe gives a block's histogram at element sizes 1, 2 and 4 in one pass
-(``rank_probe_kernel`` in csrc/rankprobe.hip, ``probe_counts_cpu`` its numpy
+(``ma_rank_probe`` in csrc/rankhist.hip, ``probe_counts_cpu`` its numpy
 twin) and ``choose_elem_size`` picks the size whose container comes out
 smallest, or none. ``devcodec`` does this under ``fpcodec.AUTO`` and hands the
 winning histogram on to the encoder, which then runs no histogram launch.
@@ -32,7 +32,7 @@ _TIE_ORDER = (2, 4, 1)
 def probe_counts_cpu(data: Any) -> tuple[Any, Any, Any]:
     """(counts1, counts2, counts4): the histograms ``rankcodec.block_order``
     sorts at ``es`` 1, 2 and 4, 256 int64 counts each. The numpy twin of
-    ``rank_probe_kernel``."""
+    ``ma_rank_probe``."""
     data = np.frombuffer(memoryview(data).cast("B"), dtype=np.uint8)
     n = len(data)
     return (

@@ -72,8 +72,7 @@ class Format:
     elem_sizes: tuple  # the element sizes a container of this format may have
     sizes_text: str  # how the element-size error names them
     label: str  # the kernels' name in error messages
-    rank_entry: str  # library entries: histogram + rank tables,
-    encode_entry: str  # segments -> stride slots,
+    encode_entry: str  # library entries: segments -> stride slots,
     decode_entry: str  # a run of containers -> raw bytes
     es_in_abi: bool  # those entries take the element size (False: they know it)
     min_hi: int = 2  # the fewest bytes a coded segment has after its low bytes
@@ -251,17 +250,6 @@ class Format:
     # GPU paths
     # -----------------------------------------------------------------------
 
-    def _launch_rank(
-        self, lib: Any, es: int, base: int, src_off: int, raw_len: int, counts: int,
-        *tables_and_stream: Any,
-    ) -> int:
-        """The histogram + rank launch of ``rank_entry`` at ``es``; a format
-        whose element sizes are ranked by different entries overrides it."""
-        es_arg = (es,) if self.es_in_abi else ()
-        return getattr(lib, self.rank_entry)(
-            base, src_off, raw_len, *es_arg, counts, *tables_and_stream
-        )
-
     def compress_spans_gpu(
         self, lib: Any, base: int, spans: Sequence[tuple[int, int]], es: int, ws: Workspace,
         counts: Any = None,
@@ -289,8 +277,8 @@ class Format:
         order_d, rank_d = tables[0], tables[1]
         if counts is None:
             counts = torch.zeros(len(spans) * 256, dtype=torch.int32, device="cuda")
-            rc = self._launch_rank(
-                lib, es, base, src_off_d.data_ptr(), raw_d.data_ptr(), counts.data_ptr(),
+            rc = lib.ma_rank_hist(
+                base, src_off_d.data_ptr(), raw_d.data_ptr(), es, counts.data_ptr(),
                 order_d.data_ptr(), rank_d.data_ptr(), len(spans), stream,
             )
         else:

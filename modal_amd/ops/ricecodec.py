@@ -132,12 +132,6 @@ class _RiceFormat(rankcodec.Format):
     """``rankcodec.Format`` with MARC10's segment layout: its device paths
     and header, this module's numpy codec and checks."""
 
-    def _launch_rank(self, lib: Any, es: int, base: int, *rest: Any) -> int:
-        # the histogram kernels are MAFB10's at es 1 and MAFP10's at 2 and 4
-        if es == 1:
-            return lib.ma_bytez_rank(base, *rest)
-        return lib.ma_fpz_rank(base, rest[0], rest[1], es, *rest[2:])
-
     # -- what a reader checks ------------------------------------------------
 
     def _segment_fields(self, buf: Any, hdr: Header) -> tuple:
@@ -295,7 +289,7 @@ class _RiceFormat(rankcodec.Format):
 
 
 FORMAT = _RiceFormat(
-    MAGIC, ELEM_SIZES, "1, 2 or 4", "ricez", "ma_fpz_rank", "ma_ricez_encode", "ma_ricez_decode",
+    MAGIC, ELEM_SIZES, "1, 2 or 4", "ricez", "ma_ricez_encode", "ma_ricez_decode",
     es_in_abi=True, min_hi=HI_FIXED,
 )
 

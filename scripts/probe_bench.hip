@@ -1,12 +1,14 @@
-// Stand-alone timing of the three-way probe (csrc/rankprobe.hip) beside the two
-// kernels it stands for, fpz_probe_kernel and bytez_hist_kernel, on the same
-// 64 MiB: hipEvent times around each launch, the kernels alternating, median
-// of 10 after 2 warm-ups, in 8 x 8 MiB and 64 x 1 MiB spans, then every table
-// of the probe compared with the other two kernels'. The figures of
-// profiles/README.md, "Three-way probe", come from it.
+// Stand-alone timing of the five instances of the histogram kernel
+// (csrc/rankhist.hip) through their entries, on the same 64 MiB: ma_rank_hist
+// at element size 1, 2 and 4 (the histogram and the rank pass behind it),
+// ma_fpz_probe and ma_rank_probe. hipEvent times around each call, the
+// entries alternating, median of 10 after 2 warm-ups, in 8 x 8 MiB and
+// 64 x 1 MiB spans, then every table of the five compared with the three-way
+// probe's. The figures of profiles/README.md, "One histogram kernel", come
+// from it.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Xclang -target-feature \
-//       -Xclang -packed-fp32-ops [-DRP_COPIES=8] scripts/probe_bench.hip -o probe_bench
+//       -Xclang -packed-fp32-ops scripts/probe_bench.hip -o probe_bench
 //   probe_bench bf16.bin e4m3.bin
 //
 // Each input is 64 MiB of raw bytes, e.g. from torch:
@@ -14,9 +16,7 @@
 //   x[: 32 << 20].to(torch.bfloat16).view(torch.uint8).numpy().tofile("bf16.bin")
 //   x.to(torch.float8_e4m3fn).view(torch.uint8).numpy().tofile("e4m3.bin")
 
-#include "../modal_amd/ops/csrc/fpz.hip"
-#include "../modal_amd/ops/csrc/bytez.hip"
-#include "../modal_amd/ops/csrc/rankprobe.hip"
+#include "../modal_amd/ops/csrc/rankhist.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -70,7 +70,6 @@ int main(int argc, char** argv) {
   uint8_t* src = dev_alloc<uint8_t>(TOTAL);
   CK(hipEventCreate(&e0));
   CK(hipEventCreate(&e1));
-  printf("RP_COPIES %d\n", RP_COPIES);
   for (int f = 1; f < argc; ++f) {
     FILE* fp = fopen(argv[f], "rb");
     if (!fp || fread(host.data(), 1, TOTAL, fp) != TOTAL) return printf("cannot read %s\n", argv[f]), 1;
@@ -82,46 +81,46 @@ int main(int argc, char** argv) {
       for (int k = 0; k < n; ++k) offs[k] = k * len;
       int64_t* d_off = dev_alloc(n, offs.data());
       int64_t* d_len = dev_alloc(n, lens.data());
-      // the probe's tables on its own grid rule and on 64 groups, the two-way
-      // probe's, the byte histogram's
-      const size_t rows[4] = {768, 768, 512, 256};
-      uint32_t* c[4];
-      std::vector<uint32_t> h[4];
-      for (int k = 0; k < 4; ++k) c[k] = dev_alloc<uint32_t>(n * rows[k]);
-      Times t[4];
+      uint8_t* order = dev_alloc<uint8_t>(n * 256);
+      uint8_t* rank_of = dev_alloc<uint8_t>(n * 256);
+      // ma_rank_hist at es 1, 2 and 4, the two-way probe, the three-way probe
+      const int es[3] = {1, 2, 4};
+      const size_t rows[5] = {256, 256, 256, 512, 768};
+      uint32_t* c[5];
+      std::vector<uint32_t> h[5];
+      for (int k = 0; k < 5; ++k) c[k] = dev_alloc<uint32_t>(n * rows[k]);
+      Times t[5];
       for (int it = 0; it < 12; ++it) {
-        for (int k = 0; k < 4; ++k) CK(hipMemset(c[k], 0, n * rows[k] * 4));
+        for (int k = 0; k < 5; ++k) CK(hipMemset(c[k], 0, n * rows[k] * 4));
         CK(hipDeviceSynchronize());
-        timed(t[0], it >= 2, [&] { ma_rank_probe(src, d_off, d_len, c[0], n, 0); });
-        timed(t[2], it >= 2, [&] { ma_fpz_probe(src, d_off, d_len, c[2], n, 0); });
-        timed(t[3], it >= 2, [&] {
-          hipLaunchKernelGGL(bytez_hist_kernel, dim3(BZ_HIST_GROUPS, n), dim3(BZ_HIST_BLOCK), 0, 0,
-                             (const uint8_t*)src, (const int64_t*)d_off, (const int64_t*)d_len, c[3], 0);
-        });
-        timed(t[1], it >= 2, [&] {
-          hipLaunchKernelGGL(rank_probe_kernel, dim3(RP_MAX_GROUPS, n), dim3(RP_BLOCK), 0, 0,
-                             (const uint8_t*)src, (const int64_t*)d_off, (const int64_t*)d_len, c[1], 0);
-        });
+        for (int k = 0; k < 3; ++k)
+          timed(t[k], it >= 2, [&] {
+            ma_rank_hist(src, d_off, d_len, es[k], c[k], order, rank_of, n, 0);
+          });
+        timed(t[3], it >= 2, [&] { ma_fpz_probe(src, d_off, d_len, c[3], n, 0); });
+        timed(t[4], it >= 2, [&] { ma_rank_probe(src, d_off, d_len, c[4], n, 0); });
       }
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < 5; ++k) {
         h[k].resize(n * rows[k]);
         CK(hipMemcpy(h[k].data(), c[k], n * rows[k] * 4, hipMemcpyDeviceToHost));
         CK(hipFree(c[k]));
       }
-      bool same = h[0] == h[1];
+      bool same = true;
       for (int k = 0; k < n; ++k)
-        for (int b = 0; b < 256; ++b)
-          same = same && h[0][k * 768 + b] == h[3][k * 256 + b] &&
-                 h[0][k * 768 + 256 + b] == h[2][k * 512 + b] &&
-                 h[0][k * 768 + 512 + b] == h[2][k * 512 + 256 + b];
+        for (int b = 0; b < 256; ++b) {
+          const uint32_t* three = &h[4][k * 768 + b];
+          same = same && h[0][k * 256 + b] == three[0] && h[1][k * 256 + b] == three[256] &&
+                 h[2][k * 256 + b] == three[512] && h[3][k * 512 + b] == three[256] &&
+                 h[3][k * 512 + 256 + b] == three[512];
+        }
       printf("  %s, %d x %lld MiB: tables %s\n", argv[f], n, (long long)(len >> 20),
              same ? "equal" : "DIFFER");
-      t[0].print("rank_probe_kernel");
-      t[1].print("rank_probe_kernel, 64 groups");
-      t[2].print("fpz_probe_kernel");
-      t[3].print("bytez_hist_kernel");
-      CK(hipFree(d_off));
-      CK(hipFree(d_len));
+      t[0].print("ma_rank_hist, es 1");
+      t[1].print("ma_rank_hist, es 2");
+      t[2].print("ma_rank_hist, es 4");
+      t[3].print("ma_fpz_probe");
+      t[4].print("ma_rank_probe");
+      for (void* p : {(void*)d_off, (void*)d_len, (void*)order, (void*)rank_of}) CK(hipFree(p));
       if (!same) return 4;
     }
   }

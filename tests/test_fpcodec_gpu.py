@@ -31,7 +31,7 @@ def _feature():
     from modal_amd.ops import devcodec, fpcodec, load_lib
 
     lib = load_lib(required=True)
-    for symbol in ("ma_fpz_rank", "ma_fpz_encode", "ma_rank_assemble", "ma_fpz_decode"):
+    for symbol in ("ma_rank_hist", "ma_fpz_encode", "ma_rank_assemble", "ma_fpz_decode"):
         getattr(lib, symbol)
     return devcodec, fpcodec, lib
 

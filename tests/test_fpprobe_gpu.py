@@ -1,4 +1,4 @@
-"""The element-size probe on the GPU (fpz_probe_kernel in csrc/fpz.hip and its
+"""The element-size probe on the GPU (ma_fpz_probe in csrc/rankhist.hip and its
 callers): both histograms against the numpy twin at every source alignment,
 more spans than one grid holds, the encoder fed the probe's tables against
 the numpy model byte for byte, ``fpcodec.AUTO`` through the device block

@@ -1,4 +1,4 @@
-"""The three-way probe on the GPU (rank_probe_kernel, csrc/rankprobe.hip) and
+"""The three-way probe on the GPU (ma_rank_probe, csrc/rankhist.hip) and
 its callers, every comparison exact."""
 
 import pickle
