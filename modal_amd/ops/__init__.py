@@ -57,6 +57,11 @@ def load_lib(required: bool = False) -> Optional[ctypes.CDLL]:
             ]
             lib.ma_lz4_compress_wave.restype = ctypes.c_int
             lib.ma_lz4_compress_wave.argtypes = lib.ma_lz4_compress.argtypes
+            lib.ma_lz4_compress_spans.restype = ctypes.c_int
+            lib.ma_lz4_compress_spans.argtypes = (
+                [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_long, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+            )
             lib.ma_lz4_decompress.restype = ctypes.c_int
             lib.ma_lz4_decompress.argtypes = [
                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -14,17 +14,17 @@ import tempfile
 _THIS_DIR = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_THIS_DIR, "csrc")
 SOURCES = ["sha256.hip", "pack.hip", "lz4.hip", "rawmem.hip", "malz.hip", "fpz.hip", "bytez.hip",
-           "ricez.hip", "lz4w.hip", "sha256w.hip", "rankhist.hip"]
-HEADERS = ["malz_common.h", "rank_common.h"]  # included by SOURCES: a change rebuilds
+           "ricez.hip", "lz4w.hip", "sha256w.hip", "rankhist.hip", "lz4s.hip"]
+HEADERS = ["malz_common.h", "rank_common.h", "lz4_lane.h", "lz4_wave.h"]  # included by SOURCES: a change rebuilds
 # Kernel files added from now on are compiled on their own with packed fp32
 # instructions turned off, some forms of which miscompute on gfx950, and
 # linked in as objects; the files above them in SOURCES build as they always
-# did. bytez.hip, ricez.hip, lz4w.hip, sha256w.hip and rankhist.hip have no float math: they come out with the
+# did. bytez.hip, ricez.hip, lz4w.hip, sha256w.hip, rankhist.hip and lz4s.hip have no float math: they come out with the
 # same registers and no spills either way (kernel-resource-usage), the flag
 # only keeps a later float addition to them off those instructions. The host
 # pass does not know the feature and says so once per kernel; that warning is
 # harmless.
-NO_PACKED_FP32 = ["bytez.hip", "ricez.hip", "lz4w.hip", "sha256w.hip", "rankhist.hip"]
+NO_PACKED_FP32 = ["bytez.hip", "ricez.hip", "lz4w.hip", "sha256w.hip", "rankhist.hip", "lz4s.hip"]
 _NO_PACKED_FP32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 

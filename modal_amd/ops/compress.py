@@ -180,8 +180,9 @@ def compress_spans_gpu(
     lz_parser: str = "lane",
 ) -> list:
     """Containers of the device bytes ``(base + offset, raw_len)`` per span,
-    None where compression does not pay. One LZ4 launch per span, of the lane
-    encoder or with ``lz_parser`` "wave" of the wavefront encoder, then
+    None where compression does not pay. ONE LZ4 launch for all the spans
+    (csrc/lz4s.hip), of the lane parser or with ``lz_parser`` "wave" of the
+    wavefront parser, over the span tables the assemble kernel takes, then
     ``container.finish_containers``: one plan launch, ONE sync, one assemble
     launch and one D2H of the dense containers, all on the current stream."""
     import torch
@@ -189,24 +190,24 @@ def compress_spans_gpu(
     check_lz_parser(lz_parser)
     if not spans:
         return []
-    launch = lib.ma_lz4_compress_wave if lz_parser == "wave" else lib.ma_lz4_compress
     stream = torch.cuda.current_stream().cuda_stream
     first_seg, n_segs, sb = [], [], 0
-    for off, ln in spans:
+    for _off, ln in spans:
         n_seg = -(-ln // SEG_SIZE)
         if sb + n_seg > ws.n_seg:
             raise RuntimeError("compress spans exceed the workspace")
-        container.check(
-            launch(
-                base + off, ln, ws.stride.data_ptr() + sb * OUT_STRIDE,
-                ws.comp_lens.data_ptr() + sb * 4, OUT_STRIDE, n_seg, stream,
-            ),
-            "lz4 compress kernel",
-        )
         first_seg.append(sb)
         n_segs.append(n_seg)
         sb += n_seg
     first_d, raw_d, src_off_d = container.span_tables(spans, first_seg)
+    container.check(
+        lib.ma_lz4_compress_spans(
+            base, src_off_d.data_ptr(), raw_d.data_ptr(), first_d.data_ptr(), len(spans), sb,
+            ws.stride.data_ptr(), OUT_STRIDE, ws.comp_lens.data_ptr(),
+            LZ_PARSERS.index(lz_parser), stream,
+        ),
+        "lz4 compress kernel",
+    )
 
     def assemble(out_off_d: Any) -> None:
         rc = lib.ma_malz_assemble(
