@@ -12,9 +12,6 @@
 //   assemble  rank_assemble_kernel (fpz.hip), given this magic and es = 1
 //   decode    one wavefront per segment of a run of containers
 //
-// Encode and decode run one wavefront per workgroup, so __syncthreads() is a
-// wave-level LDS fence and every branch around it is wave-uniform.
-//
 // Data path. fpz.hip reads strided top bytes out of a staged segment; here
 // there is no stride, so a segment is staged into LDS AT OFFSET 0 (aligned
 // dword loads, funnel-shifted by the source misalignment on the way in) and
@@ -56,7 +53,6 @@
 // LDS busy under 2 % of the wave cycles; the per-element code extraction and
 // the stores are what is left. More in profiles/README.md, "Byte-plane codec".
 
-#include "malz_common.h"
 #include "rank_common.h"
 
 #define BZ_RUN_DWORDS 16  // a lane's run is at most 64 bytes
@@ -64,10 +60,9 @@
 // of the last code bytes may touch behind them
 #define BZ_IN_DWORDS (SEG_SIZE / 4 + SEG_SIZE / 64 + 4)
 
-__device__ __forceinline__ int padw(int k) { return k + (k >> 4); }           // dword k
-__device__ __forceinline__ int padb(int i) { return i + ((i >> 6) << 2); }    // byte i
+__device__ __forceinline__ int padw(int k) { return k + (k >> 4); }  // dword k; byte i: pad(i)
 
-// len bytes at src -> LDS so that byte i of the segment is byte padb(i):
+// len bytes at src -> LDS so that byte i of the segment is byte pad(i):
 // aligned dword loads, each lane's dword completed with the next lane's.
 // Every dword loaded holds at least one of the segment's own bytes.
 __device__ __forceinline__ void stage_at_zero(const uint8_t* __restrict__ src, int len,
@@ -112,23 +107,17 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_encode_kernel(
   __shared__ uint32_t rank32[256 / 4];
   const uint8_t* rank = reinterpret_cast<const uint8_t*>(rank32);
   const int lane = threadIdx.x;
-  const int bk = blk_base + blockIdx.y;
-  const int64_t raw_len = blk_raw_len[bk];
-  const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
-  const int64_t first = blk_first_seg[bk];
-  const uint8_t* blk_src = src + blk_src_off[bk];
-  if ((int64_t)blockIdx.x >= n_seg) return;
-  rank32[lane] = reinterpret_cast<const uint32_t*>(rank_tab + (int64_t)bk * 256)[lane];
+  const RankBlock blk = rank_block(src, blk_src_off, blk_raw_len, blk_first_seg, rank_tab,
+                                   blk_base, rank32, lane);
+  if ((int64_t)blockIdx.x >= blk.n_seg) return;
 
-  for (int64_t s = blockIdx.x; s < n_seg; s += gridDim.x) {
+  for (int64_t s = blockIdx.x; s < blk.n_seg; s += gridDim.x) {
     __syncthreads();  // the last segment's readers are done; rank is visible
-    const int m = seg_eff(0, raw_len, s);
-    int32_t* clen = comp_lens + first + s;
-    if (m < 3) {  // hi >= 2, so fewer than 3 elements never code
-      if (lane == 0) *clen = 0;
-      continue;
-    }
-    stage_at_zero(blk_src + s * SEG_SIZE, m, in32, lane);
+    const int m = seg_eff(0, blk.raw_len, s);
+    int32_t* clen = comp_lens + blk.first + s;
+    // hi >= 2, so fewer than 3 elements never code
+    if (m < 3) { decline(clen, lane); continue; }
+    stage_at_zero(blk.src + s * SEG_SIZE, m, in32, lane);
     __syncthreads();
 
     const int per = lane_run(m);
@@ -182,14 +171,11 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_encode_kernel(
       const int cost = 1 + ((m * w + 7) >> 3) + total[w - 1];
       if (cost < hi) { hi = cost; b = w; my_esc = mine[w - 1]; }
     }
-    if (b == 0) {
-      if (lane == 0) *clen = 0;
-      continue;
-    }
+    if (b == 0) { decline(clen, lane); continue; }
 
     const uint32_t E = (1u << b) - 1;
     const int nbytes = (m * b + 7) >> 3;
-    uint8_t* out = stride_buf + (first + s) * out_stride;
+    uint8_t* out = stride_buf + (blk.first + s) * out_stride;
     uint8_t* escs = out + 1 + nbytes + wave_excl_scan(my_esc, lane);
     // v[g]: the b code bytes of the lane's g-th group of 8 elements
     uint64_t v[BZ_RUN_DWORDS / 2];
@@ -259,10 +245,6 @@ __device__ __forceinline__ uint64_t lds_bytes8(const uint32_t* in32, int at) {
   return ((uint64_t)hi << 32) | lo;
 }
 
-// *status comes in as INT32_MAX and leaves as the min of seg + 1 over the
-// segments that are malformed (untouched: none). A malformed segment writes
-// nothing; no segment reads outside its seg_len bytes (rounded out to aligned
-// dwords) or writes outside its raw bytes.
 extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
     const uint8_t* __restrict__ comp, const int64_t* __restrict__ comp_offs,
     const int64_t* __restrict__ dst_offs, const int32_t* __restrict__ seg_lens,
@@ -278,28 +260,17 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
 
   for (int seg = blockIdx.x; seg < n_segments; seg += gridDim.x) {
     __syncthreads();  // the last segment's LDS readers are done
-    const uint8_t* sp = comp + comp_offs[seg];
-    uint8_t* d = dst + dst_offs[seg];
-    const int m = seg_raw[seg];
-    const int slen = seg_lens[seg];
-    bool ok = m > 0 && m <= SEG_SIZE;
-    if (ok && slen == 0) {  // stored raw
-      wave_copy(sp, d, m, lane);
+    RankSeg sg;  // es = 1: m = L, no low plane
+    if (!rank_seg<1 << 1, 2>(sg, seg, comp, comp_offs, dst_offs, seg_lens, seg_raw, seg_blk,
+                             nullptr, dst, status, lane))
       continue;
-    }
-    ok = ok && slen >= 2 && slen < m;
-    int b = 0, nbytes = 0;
-    if (ok) {
-      order32[lane] = reinterpret_cast<const uint32_t*>(orders + (int64_t)seg_blk[seg] * 256)[lane];
-      stage_at_zero(sp, slen, in32, lane);
-    }
+    const int m = sg.m, slen = sg.slen;
+    table_in(orders, sg.blk, order32, lane);
+    stage_at_zero(sg.sp, slen, in32, lane);
     __syncthreads();
-    if (ok) {
-      b = in[0];
-      nbytes = (m * b + 7) >> 3;
-      ok = b >= 1 && b <= 7 && 1 + nbytes <= slen;
-    }
-    if (!ok) b = 0;
+    const int b = in[0];
+    const int nbytes = (m * b + 7) >> 3;
+    if (b < 1 || b > 7 || 1 + nbytes > slen) { malformed(status, seg, lane); continue; }
     const int per = lane_run(m);
     const int ndw = per >> 2, ngrp = per >> 3;
     const int i0 = lane * per;
@@ -309,7 +280,7 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
 #pragma unroll
     for (int g = 0; g < BZ_RUN_DWORDS / 2; ++g) {
       v[g] = 0;
-      if (ok && g < ngrp && i0 + 8 * g < m) {
+      if (g < ngrp && i0 + 8 * g < m) {
         v[g] = lds_bytes8(in32, 1 + ((i0 >> 3) + g) * b);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
@@ -317,11 +288,7 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
       }
     }
     // the escapes must be exactly what is left of seg_len
-    ok = ok && wave_sum(my_esc) == slen - 1 - nbytes;
-    if (!ok) {
-      if (lane == 0) atomicMin(status, seg + 1);  // the FIRST malformed one
-      continue;
-    }
+    if (wave_sum(my_esc) != slen - 1 - nbytes) { malformed(status, seg, lane); continue; }
     int esc_at = 1 + nbytes + wave_excl_scan(my_esc, lane);
     uint32_t o[BZ_RUN_DWORDS];
 #pragma unroll
@@ -332,15 +299,15 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
         for (int k = 0; k < 4; ++k)
           if (i0 + 4 * q + k < m) {
             const uint32_t code = (uint32_t)(v[q >> 1] >> ((4 * (q & 1) + k) * b)) & E;
-            const uint32_t byte = code == E ? in[padb(esc_at++)] : order[code];
+            const uint32_t byte = code == E ? in[pad(esc_at++)] : order[code];
             o[q] |= byte << (8 * k);
           }
       }
     }
     // whole runs to a 16-byte aligned destination: straight from registers
-    const bool direct = (reinterpret_cast<uintptr_t>(d) & 15) == 0 && (per & 15) == 0 && m % per == 0;
+    const bool direct = (reinterpret_cast<uintptr_t>(sg.d) & 15) == 0 && (per & 15) == 0 && m % per == 0;
     if (direct) {
-      uint4* d4 = reinterpret_cast<uint4*>(d + i0);
+      uint4* d4 = reinterpret_cast<uint4*>(sg.d + i0);
 #pragma unroll
       for (int q = 0; q < BZ_RUN_DWORDS / 4; ++q)
         if (4 * q < ndw && i0 < m) d4[q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
@@ -349,7 +316,7 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
       for (int q = 0; q < BZ_RUN_DWORDS; ++q)
         if (q < ndw && i0 + 4 * q < m) out32[(i0 >> 2) + q] = o[q];
       __syncthreads();
-      lds_to_global(reinterpret_cast<const uint8_t*>(out32), d, m, lane);
+      lds_to_global(reinterpret_cast<const uint8_t*>(out32), sg.d, m, lane);
     }
   }
 }
@@ -358,32 +325,19 @@ extern "C" __global__ __launch_bounds__(WAVE) void bytez_decode_kernel(
 // host entry points
 // ---------------------------------------------------------------------------
 
-// max_segs: the largest segment count of any block (bounds the grid).
 extern "C" int ma_bytez_encode(const void* src, const void* blk_src_off,
                                const void* blk_raw_len, const void* blk_first_seg,
                                const void* rank_of, void* stride_buf, int out_stride,
                                void* comp_lens, int n_blocks, long max_segs, void* stream) {
-  if (n_blocks <= 0 || max_segs <= 0) return 0;
-  const int gx = (int)(max_segs < 16384 ? max_segs : 16384);
-  return launch_chunked(n_blocks, [&](int base, int ny) {
-    hipLaunchKernelGGL(bytez_encode_kernel, dim3(gx, ny), dim3(WAVE), 0, (hipStream_t)stream,
-                       (const uint8_t*)src, (const int64_t*)blk_src_off,
-                       (const int64_t*)blk_raw_len, (const int32_t*)blk_first_seg,
-                       (const uint8_t*)rank_of, (uint8_t*)stride_buf, out_stride,
-                       (int32_t*)comp_lens, base);
-  });
+  return launch_rank_encode(bytez_encode_kernel, true, n_blocks, max_segs, stream, src,
+                            blk_src_off, blk_raw_len, blk_first_seg, rank_of, stride_buf,
+                            out_stride, comp_lens);
 }
 
 extern "C" int ma_bytez_decode(const void* comp, const void* comp_offs, const void* dst_offs,
                                const void* seg_lens, const void* seg_raw, const void* seg_blk,
                                const void* orders, void* dst, void* status, int n_segments,
                                void* stream) {
-  if (n_segments <= 0) return 0;
-  const int gx = n_segments < (1 << 20) ? n_segments : (1 << 20);
-  hipLaunchKernelGGL(bytez_decode_kernel, dim3(gx), dim3(WAVE), 0, (hipStream_t)stream,
-                     (const uint8_t*)comp, (const int64_t*)comp_offs,
-                     (const int64_t*)dst_offs, (const int32_t*)seg_lens,
-                     (const int32_t*)seg_raw, (const int32_t*)seg_blk,
-                     (const uint8_t*)orders, (uint8_t*)dst, (int32_t*)status, n_segments);
-  return (int)hipGetLastError();
+  return launch_rank_decode(bytez_decode_kernel, n_segments, stream, comp, comp_offs, dst_offs,
+                            seg_lens, seg_raw, seg_blk, orders, dst, status);
 }

@@ -14,9 +14,6 @@
 //             and MAFB10, which gives it its magic and es = 1
 //   decode    one wavefront per segment of a run of containers
 //
-// Encode and decode run one wavefront per workgroup, so __syncthreads() is a
-// wave-level LDS fence and every branch around it is wave-uniform.
-//
 // Staging. A lane owns a RUN of consecutive elements (32 of a full bf16
 // segment), so that its codes are whole bytes and its escapes are contiguous.
 // Read straight from global memory that would be 64 lanes 64 bytes apart per
@@ -29,8 +26,9 @@
 // apart and do conflict; at 4 KiB per wavefront that is far below the cost of
 // the global traffic and is left alone.
 
-#include "malz_common.h"
 #include "rank_common.h"
+
+#define FPZ_ES_MASK (1 << 2 | 1 << 4)  // element sizes 2 and 4
 
 // ---------------------------------------------------------------------------
 // encode: one wavefront per segment
@@ -47,24 +45,18 @@ extern "C" __global__ __launch_bounds__(WAVE) void fpz_encode_kernel(
   const uint8_t* in = reinterpret_cast<const uint8_t*>(in32);
   const uint8_t* rank = reinterpret_cast<const uint8_t*>(rank32);
   const int lane = threadIdx.x;
-  const int bk = blk_base + blockIdx.y;
-  const int64_t raw_len = blk_raw_len[bk];
-  const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
-  const int64_t first = blk_first_seg[bk];
-  const uint8_t* blk_src = src + blk_src_off[bk];
-  if ((int64_t)blockIdx.x >= n_seg) return;
-  rank32[lane] = reinterpret_cast<const uint32_t*>(rank_tab + (int64_t)bk * 256)[lane];
+  const RankBlock blk = rank_block(src, blk_src_off, blk_raw_len, blk_first_seg, rank_tab,
+                                   blk_base, rank32, lane);
+  if ((int64_t)blockIdx.x >= blk.n_seg) return;
 
-  for (int64_t s = blockIdx.x; s < n_seg; s += gridDim.x) {
+  for (int64_t s = blockIdx.x; s < blk.n_seg; s += gridDim.x) {
     __syncthreads();  // the last segment's readers are done; rank is visible
-    const int L = seg_eff(0, raw_len, s);
+    const int L = seg_eff(0, blk.raw_len, s);
     const int m = L / es;
-    int32_t* clen = comp_lens + first + s;
-    if (L % es != 0 || m < 3) {  // hi >= 2, so fewer than 3 elements never code
-      if (lane == 0) *clen = 0;
-      continue;
-    }
-    const int mis = stage_in(blk_src + s * SEG_SIZE, L, in32, lane);
+    int32_t* clen = comp_lens + blk.first + s;
+    // hi >= 2, so fewer than 3 elements never code
+    if (L % es != 0 || m < 3) { decline(clen, lane); continue; }
+    const int mis = stage_in(blk.src + s * SEG_SIZE, L, in32, lane);
     __syncthreads();
 
     const int per = lane_run(m);
@@ -84,32 +76,13 @@ extern "C" __global__ __launch_bounds__(WAVE) void fpz_encode_kernel(
       const int cost = 1 + ((m * w + 7) >> 3) + wave_sum(mine[w - 1]);
       if (cost < hi) { hi = cost; b = w; my_esc = mine[w - 1]; }
     }
-    if (b == 0) {
-      if (lane == 0) *clen = 0;
-      continue;
-    }
+    if (b == 0) { decline(clen, lane); continue; }
 
     const int E = (1 << b) - 1;
     const int lo = m * (es - 1);
     const int nbytes = (m * b + 7) >> 3;
-    uint8_t* out = stride_buf + (first + s) * out_stride;
-    // low bytes of every element, four output bytes per store when the slot
-    // allows (it does for a Workspace: aligned base, stride a multiple of 256)
-    const int lo_vec = (reinterpret_cast<uintptr_t>(out) & 3) == 0 ? lo >> 2 : 0;
-    for (int q = lane; q < lo_vec; q += WAVE) {
-      uint32_t v = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int o = 4 * q + k;
-        const int i = es == 2 ? o : o / 3;
-        v |= (uint32_t)in[pad(mis + i * es + (o - i * (es - 1)))] << (8 * k);
-      }
-      reinterpret_cast<uint32_t*>(out)[q] = v;
-    }
-    for (int o = 4 * lo_vec + lane; o < lo; o += WAVE) {
-      const int i = es == 2 ? o : o / 3;
-      out[o] = in[pad(mis + i * es + (o - i * (es - 1)))];
-    }
+    uint8_t* out = stride_buf + (blk.first + s) * out_stride;
+    low_bytes_out(in, mis, es, lo, out, lane);
     if (lane == 0) out[lo] = (uint8_t)b;
 
     uint8_t* codes = out + lo + 1;
@@ -179,10 +152,6 @@ __device__ __forceinline__ uint64_t load_codes(const uint8_t* in, int at, int cb
   return v;
 }
 
-// *status comes in as INT32_MAX and leaves as the min of seg + 1 over the
-// segments that are malformed (untouched: none). A malformed segment writes
-// nothing; no segment reads outside its seg_len bytes (rounded out to aligned
-// dwords) or writes outside its raw bytes.
 extern "C" __global__ __launch_bounds__(WAVE) void fpz_decode_kernel(
     const uint8_t* __restrict__ comp, const int64_t* __restrict__ comp_offs,
     const int64_t* __restrict__ dst_offs, const int32_t* __restrict__ seg_lens,
@@ -199,51 +168,29 @@ extern "C" __global__ __launch_bounds__(WAVE) void fpz_decode_kernel(
 
   for (int seg = blockIdx.x; seg < n_segments; seg += gridDim.x) {
     __syncthreads();  // the last segment's LDS readers are done
-    const uint8_t* sp = comp + comp_offs[seg];
-    uint8_t* d = dst + dst_offs[seg];
-    const int L = seg_raw[seg];
-    const int slen = seg_lens[seg];
-    bool ok = L > 0 && L <= SEG_SIZE;
-    if (ok && slen == 0) {  // stored raw
-      wave_copy(sp, d, L, lane);
+    RankSeg sg;
+    if (!rank_seg<FPZ_ES_MASK, 2>(sg, seg, comp, comp_offs, dst_offs, seg_lens, seg_raw, seg_blk,
+                                  blk_es, dst, status, lane))
       continue;
-    }
-    const int blk = seg_blk[seg];
-    const int es = blk_es[blk];
-    ok = ok && (es == 2 || es == 4);
-    const int m = ok ? L / es : 0;
-    const int lo = m * (es - 1);
-    ok = ok && L % es == 0 && slen >= lo + 2 && slen < L;
-    int mis = 0, b = 0, nbytes = 0;
-    if (ok) {
-      order32[lane] = reinterpret_cast<const uint32_t*>(orders + (int64_t)blk * 256)[lane];
-      mis = stage_in(sp, slen, in32, lane);
-    }
+    const int es = sg.es, m = sg.m, lo = sg.lo, slen = sg.slen;
+    table_in(orders, sg.blk, order32, lane);
+    const int mis = stage_in(sg.sp, slen, in32, lane);
     __syncthreads();
-    if (ok) {
-      b = in[pad(mis + lo)];
-      nbytes = (m * b + 7) >> 3;
-      ok = b >= 1 && b <= 7 && lo + 1 + nbytes <= slen;
-    }
-    if (!ok) b = 0;
+    const int b = in[pad(mis + lo)];
+    const int nbytes = (m * b + 7) >> 3;
+    if (b < 1 || b > 7 || lo + 1 + nbytes > slen) { malformed(status, seg, lane); continue; }
     const int per = lane_run(m);
     const int i0 = lane * per;
     const int E = (1 << b) - 1;
     const int at = mis + lo + 1;  // the code stream
     int my_esc = 0;
-    if (ok) {
-      for (int g = 0; g * 8 < per; ++g) {
-        const uint64_t v = load_codes(in, at, ((i0 >> 3) + g) * b, b, nbytes);
-        for (int j = 0; j < 8; ++j)
-          my_esc += (i0 + g * 8 + j < m) && (int)((v >> (j * b)) & E) == E;
-      }
-      // the escapes must be exactly what is left of seg_len
-      ok = wave_sum(my_esc) == slen - lo - 1 - nbytes;
+    for (int g = 0; g * 8 < per; ++g) {
+      const uint64_t v = load_codes(in, at, ((i0 >> 3) + g) * b, b, nbytes);
+      for (int j = 0; j < 8; ++j)
+        my_esc += (i0 + g * 8 + j < m) && (int)((v >> (j * b)) & E) == E;
     }
-    if (!ok) {
-      if (lane == 0) atomicMin(status, seg + 1);  // the FIRST malformed one
-      continue;
-    }
+    // the escapes must be exactly what is left of seg_len
+    if (wave_sum(my_esc) != slen - lo - 1 - nbytes) { malformed(status, seg, lane); continue; }
     int esc_at = at + nbytes + wave_excl_scan(my_esc, lane);
     for (int g = 0; g * 8 < per; ++g) {
       const uint64_t v = load_codes(in, at, ((i0 >> 3) + g) * b, b, nbytes);
@@ -255,12 +202,9 @@ extern "C" __global__ __launch_bounds__(WAVE) void fpz_decode_kernel(
         }
       }
     }
-    for (int o = lane; o < lo; o += WAVE) {
-      const int i = es == 2 ? o : o / 3;
-      outb[i * es + (o - i * (es - 1))] = in[pad(mis + o)];
-    }
+    low_bytes_in(in, mis, es, lo, outb, lane);
     __syncthreads();
-    lds_to_global(outb, d, L, lane);
+    lds_to_global(outb, sg.d, sg.L, lane);
   }
 }
 
@@ -268,21 +212,13 @@ extern "C" __global__ __launch_bounds__(WAVE) void fpz_decode_kernel(
 // host entry points
 // ---------------------------------------------------------------------------
 
-// max_segs: the largest segment count of any block (bounds the grid).
 extern "C" int ma_fpz_encode(const void* src, const void* blk_src_off,
                              const void* blk_raw_len, const void* blk_first_seg,
                              const void* rank_of, int es, void* stride_buf, int out_stride,
                              void* comp_lens, int n_blocks, long max_segs, void* stream) {
-  if (n_blocks <= 0 || max_segs <= 0) return 0;
-  if (es != 2 && es != 4) return (int)hipErrorInvalidValue;
-  const int gx = (int)(max_segs < 16384 ? max_segs : 16384);
-  return launch_chunked(n_blocks, [&](int base, int ny) {
-    hipLaunchKernelGGL(fpz_encode_kernel, dim3(gx, ny), dim3(WAVE), 0, (hipStream_t)stream,
-                       (const uint8_t*)src, (const int64_t*)blk_src_off,
-                       (const int64_t*)blk_raw_len, (const int32_t*)blk_first_seg,
-                       (const uint8_t*)rank_of, es, (uint8_t*)stride_buf, out_stride,
-                       (int32_t*)comp_lens, base);
-  });
+  return launch_rank_encode(fpz_encode_kernel, es == 2 || es == 4, n_blocks, max_segs, stream,
+                            src, blk_src_off, blk_raw_len, blk_first_seg, rank_of, es,
+                            stride_buf, out_stride, comp_lens);
 }
 
 // magic: the container's six magic bytes as a little-endian integer.
@@ -294,13 +230,9 @@ extern "C" int ma_rank_assemble(const void* src, const void* blk_src_off,
                                 const void* blk_out_off, int n_blocks, void* stream) {
   if (es != 1 && es != 2 && es != 4) return (int)hipErrorInvalidValue;
   return launch_chunked(n_blocks, [&](int base, int ny) {
-    hipLaunchKernelGGL(rank_assemble_kernel, dim3(ASM_GROUPS, ny), dim3(ASM_BLOCK), 0,
-                       (hipStream_t)stream, (const uint8_t*)src,
-                       (const int64_t*)blk_src_off, (const uint8_t*)stride_buf, out_stride,
-                       (const int32_t*)comp_lens, (const int64_t*)seg_off,
-                       (const int32_t*)blk_first_seg, (const int64_t*)blk_raw_len,
-                       (const uint8_t*)order, (uint64_t)magic, es, (uint8_t*)out,
-                       (const int64_t*)blk_out_off, base);
+    launch_as(rank_assemble_kernel, dim3(ASM_GROUPS, ny), ASM_BLOCK, stream, src, blk_src_off,
+              stride_buf, out_stride, comp_lens, seg_off, blk_first_seg, blk_raw_len, order,
+              magic, es, out, blk_out_off, base);
   });
 }
 
@@ -308,13 +240,6 @@ extern "C" int ma_fpz_decode(const void* comp, const void* comp_offs, const void
                              const void* seg_lens, const void* seg_raw, const void* seg_blk,
                              const void* orders, const void* blk_es, void* dst, void* status,
                              int n_segments, void* stream) {
-  if (n_segments <= 0) return 0;
-  const int gx = n_segments < (1 << 20) ? n_segments : (1 << 20);
-  hipLaunchKernelGGL(fpz_decode_kernel, dim3(gx), dim3(WAVE), 0, (hipStream_t)stream,
-                     (const uint8_t*)comp, (const int64_t*)comp_offs,
-                     (const int64_t*)dst_offs, (const int32_t*)seg_lens,
-                     (const int32_t*)seg_raw, (const int32_t*)seg_blk,
-                     (const uint8_t*)orders, (const uint8_t*)blk_es, (uint8_t*)dst,
-                     (int32_t*)status, n_segments);
-  return (int)hipGetLastError();
+  return launch_rank_decode(fpz_decode_kernel, n_segments, stream, comp, comp_offs, dst_offs,
+                            seg_lens, seg_raw, seg_blk, orders, blk_es, dst, status);
 }

@@ -1,6 +1,8 @@
-// Shared by the container kernels (malz.hip, fpz.hip) for gfx950: the raw
-// length of a segment, byte-exact wavefront copies, the segment table and
-// payload of a container, the launch loop for grids past MAX_GRID_Y rows.
+// Shared by every kernel file that works on 4 KiB segments (malz.hip; fpz.hip,
+// bytez.hip and ricez.hip through rank_common.h; rankhist.hip; the LZ4
+// encoders through lz4_lane.h and lz4_wave.h) for gfx950: the raw length of a
+// segment, byte-exact wavefront copies, the segment table and payload of a
+// container, the launch loop for grids past MAX_GRID_Y rows.
 
 #pragma once
 

@@ -11,10 +11,9 @@
 //   encode    one wavefront per segment -> its stride slot + comp_lens
 //   decode    one wavefront per segment of a run of containers
 //
-// Both run one wavefront per workgroup, so __syncthreads() is a wave-level
-// LDS fence and every branch around it is wave-uniform. Both stage a segment
-// as fpz.hip does (rank_common.h): a lane's run of a full segment is 64 bytes
-// at every element size, which is what the pad dword per 16 is for.
+// Both stage a segment as fpz.hip does (rank_common.h): a lane's run of a
+// full segment is 64 bytes at every element size, which is what the pad dword
+// per 16 is for.
 //
 // A variable-length code decodes serially, so a segment's m elements are cut
 // into 16 sub-streams of per = ceil(m/16) elements, byte-aligned, with a
@@ -38,9 +37,9 @@
 // refilled a dword at a time from the staged segment; the unary part of a
 // code is a count of trailing ones of the window. Top bytes go into an LDS
 // image of the raw segment, then all 64 lanes put the low bytes between them
-// and copy the image out. One segment to a wavefront leaves 48 lanes idle in
-// the walk and takes 9 KiB of LDS; RZ_DECODE_SEGS = 4 walks four segments at
-// once (16 lanes each) in 35 KiB, one wavefront to a SIMD.
+// and copy the image out. That leaves 48 lanes idle in the walk; a variant
+// that walked four segments per wavefront was measured, lost and removed
+// (profiles/README.md, "Rice-coded rank planes").
 //
 // Measured on an MI355X (hipEvent times, median of 10 interleaved launches,
 // 64 MiB of N(0,1) in 8 x 8 MiB spans, as bf16 beside fpz.hip and as
@@ -48,12 +47,9 @@
 // their 0.7127 and 0.8855):
 //                       es 2: ricez    fpz       es 1: ricez    bytez
 //   encode              95.2 us        65.2 us   144.6 us       99.2 us
-//   decode, 1 segment   238.4 us       82.5 us   430.6 us       105.9 us
-//   decode, 4 segments  290.9 us                 440.0 us
+//   decode              238.4 us       82.5 us   430.6 us       105.9 us
 // The serial walk is the decoder's cost, 2.9x and 4.1x the fixed-width
-// kernels; four segments to a wavefront do not hide it, they lose to the
-// occupancy of one, so one is kept. More in profiles/README.md, "Rice-coded
-// rank planes".
+// kernels. More in profiles/README.md, "Rice-coded rank planes".
 //
 // Bounds. Before any lane walks, the 16 lanes of a segment check k, that the
 // end table does not decrease and that end[15] is exactly what seg_len
@@ -63,17 +59,13 @@
 // staging buffer besides. A rank is checked against 255 before it indexes
 // the order table.
 
-#include "malz_common.h"
 #include "rank_common.h"
 
 #define RZ_SUBS 16
 #define RZ_Q_ESC 12                    // a unary run this long announces a raw byte
 #define RZ_HI_FIXED (1 + 2 * RZ_SUBS)  // k and the end table
 #define RZ_HI_DWORDS (SEG_SIZE / 4 + 2)
-#ifndef RZ_DECODE_SEGS
-#define RZ_DECODE_SEGS 1  // segments per wavefront in decode: 1 or 4
-#endif
-#define RZ_GROUP (WAVE / 4)  // lanes that walk one segment
+#define RZ_ES_MASK (1 << 1 | 1 << 2 | 1 << 4)  // element sizes 1, 2 and 4
 // the last dword a window refill may name, and a staging buffer that has it
 #define RZ_MAX_DW ((SEG_SIZE + 3 + 3) / 4 + 8)
 #define RZ_IN_DWORDS (IN_DWORDS + 16)
@@ -96,24 +88,18 @@ extern "C" __global__ __launch_bounds__(WAVE) void ricez_encode_kernel(
   const uint8_t* rank = reinterpret_cast<const uint8_t*>(rank32);
   const int lane = threadIdx.x;
   const int sub = lane >> 2, quarter = lane & 3;
-  const int bk = blk_base + blockIdx.y;
-  const int64_t raw_len = blk_raw_len[bk];
-  const int64_t n_seg = (raw_len + SEG_SIZE - 1) / SEG_SIZE;
-  const int64_t first = blk_first_seg[bk];
-  const uint8_t* blk_src = src + blk_src_off[bk];
-  if ((int64_t)blockIdx.x >= n_seg) return;
-  rank32[lane] = reinterpret_cast<const uint32_t*>(rank_tab + (int64_t)bk * 256)[lane];
+  const RankBlock blk = rank_block(src, blk_src_off, blk_raw_len, blk_first_seg, rank_tab,
+                                   blk_base, rank32, lane);
+  if ((int64_t)blockIdx.x >= blk.n_seg) return;
 
-  for (int64_t s = blockIdx.x; s < n_seg; s += gridDim.x) {
+  for (int64_t s = blockIdx.x; s < blk.n_seg; s += gridDim.x) {
     __syncthreads();  // the last segment's readers are done; rank is visible
-    const int L = seg_eff(0, raw_len, s);
+    const int L = seg_eff(0, blk.raw_len, s);
     const int m = L / es;
-    int32_t* clen = comp_lens + first + s;
-    if (L % es != 0 || m <= RZ_HI_FIXED) {  // hi > 33, so no fewer elements ever code
-      if (lane == 0) *clen = 0;
-      continue;
-    }
-    const int mis = stage_in(blk_src + s * SEG_SIZE, L, in32, lane);
+    int32_t* clen = comp_lens + blk.first + s;
+    // hi > 33, so no fewer elements ever code
+    if (L % es != 0 || m <= RZ_HI_FIXED) { decline(clen, lane); continue; }
+    const int mis = stage_in(blk.src + s * SEG_SIZE, L, in32, lane);
     __syncthreads();
 
     const int per = (m + RZ_SUBS - 1) / RZ_SUBS;
@@ -154,10 +140,7 @@ extern "C" __global__ __launch_bounds__(WAVE) void ricez_encode_kernel(
       const int cost = RZ_HI_FIXED + total[w];
       if (cost < hi) { hi = cost; k = w; my_bits = bits[w]; my_sub_bytes = sub_bytes[w]; }
     }
-    if (k < 0) {
-      if (lane == 0) *clen = 0;
-      continue;
-    }
+    if (k < 0) { decline(clen, lane); continue; }
 
     // pass 2: where the lane's bits begin
     int off = 0;  // bits of the sub-stream's lanes before this one
@@ -215,122 +198,58 @@ extern "C" __global__ __launch_bounds__(WAVE) void ricez_encode_kernel(
     __syncthreads();
 
     const int lo = m * (es - 1);
-    uint8_t* out = stride_buf + (first + s) * out_stride;
-    // low bytes of every element, four output bytes per store when the slot
-    // allows (it does for a Workspace: aligned base, stride a multiple of 256)
-    const int lo_vec = (reinterpret_cast<uintptr_t>(out) & 3) == 0 ? lo >> 2 : 0;
-    for (int q = lane; q < lo_vec; q += WAVE) {
-      uint32_t v = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int o = 4 * q + j;
-        const int i = es == 2 ? o : o / 3;
-        v |= (uint32_t)in[pad(mis + i * es + (o - i * (es - 1)))] << (8 * j);
-      }
-      reinterpret_cast<uint32_t*>(out)[q] = v;
-    }
-    for (int o = 4 * lo_vec + lane; o < lo; o += WAVE) {
-      const int i = es == 2 ? o : o / 3;
-      out[o] = in[pad(mis + i * es + (o - i * (es - 1)))];
-    }
+    uint8_t* out = stride_buf + (blk.first + s) * out_stride;
+    low_bytes_out(in, mis, es, lo, out, lane);
     lds_to_global(hib, out + lo, hi, lane);
     if (lane == 0) *clen = lo + hi;
   }
 }
 
 // ---------------------------------------------------------------------------
-// decode: RZ_DECODE_SEGS segments per wavefront of a run of containers
+// decode: one wavefront per segment of a run of containers
 // ---------------------------------------------------------------------------
 
-struct RzSeg {
-  const uint8_t* sp;  // its bytes in the payloads
-  uint8_t* d;         // its raw bytes
-  int L, slen, blk, es, m, lo;
-  bool raw, coded;  // stored raw; or coded with lengths a decoder may index with
-};
-
-__device__ __forceinline__ RzSeg rz_seg(
-    int seg, const uint8_t* __restrict__ comp, const int64_t* __restrict__ comp_offs,
-    const int64_t* __restrict__ dst_offs, const int32_t* __restrict__ seg_lens,
-    const int32_t* __restrict__ seg_raw, const int32_t* __restrict__ seg_blk,
-    const uint8_t* __restrict__ blk_es, uint8_t* __restrict__ dst) {
-  RzSeg g;
-  g.sp = comp + comp_offs[seg];
-  g.d = dst + dst_offs[seg];
-  g.L = seg_raw[seg];
-  g.slen = seg_lens[seg];
-  g.blk = seg_blk[seg];
-  g.es = blk_es[g.blk];
-  const bool sized = g.L > 0 && g.L <= SEG_SIZE;
-  const bool typed = g.es == 1 || g.es == 2 || g.es == 4;
-  g.raw = sized && g.slen == 0;
-  g.m = typed ? g.L / g.es : 0;
-  g.lo = g.m * (g.es - 1);
-  g.coded = sized && typed && g.L % g.es == 0 && g.slen >= g.lo + RZ_HI_FIXED && g.slen < g.L;
-  return g;
-}
-
-// *status comes in as INT32_MAX and leaves as the min of seg + 1 over the
-// segments that are malformed (untouched: none). A malformed segment writes
-// nothing; no segment reads outside its seg_len bytes (rounded out to aligned
-// dwords) or writes outside its raw bytes.
 extern "C" __global__ __launch_bounds__(WAVE) void ricez_decode_kernel(
     const uint8_t* __restrict__ comp, const int64_t* __restrict__ comp_offs,
     const int64_t* __restrict__ dst_offs, const int32_t* __restrict__ seg_lens,
     const int32_t* __restrict__ seg_raw, const int32_t* __restrict__ seg_blk,
     const uint8_t* __restrict__ orders, const uint8_t* __restrict__ blk_es,
     uint8_t* __restrict__ dst, int32_t* __restrict__ status, int n_segments) {
-  __shared__ uint32_t in32[RZ_DECODE_SEGS][RZ_IN_DWORDS];
-  __shared__ __attribute__((aligned(16))) uint32_t out32[RZ_DECODE_SEGS][SEG_SIZE / 4];
-  __shared__ uint32_t order32[RZ_DECODE_SEGS][256 / 4];
+  __shared__ uint32_t in32[RZ_IN_DWORDS];
+  __shared__ __attribute__((aligned(16))) uint32_t out32[SEG_SIZE / 4];
+  __shared__ uint32_t order32[256 / 4];
+  const uint8_t* in = reinterpret_cast<const uint8_t*>(in32);
+  uint8_t* outb = reinterpret_cast<uint8_t*>(out32);
+  const uint8_t* order = reinterpret_cast<const uint8_t*>(order32);
   const int lane = threadIdx.x;
-  const int mine = lane / RZ_GROUP, sub = lane % RZ_GROUP;  // the segment and sub-stream walked
-#define RZ_SEG(seg) \
-  rz_seg(seg, comp, comp_offs, dst_offs, seg_lens, seg_raw, seg_blk, blk_es, dst)
+  const int sub = lane;  // the sub-stream a lane walks, if it walks
+  const bool walks = sub < RZ_SUBS;
 
-  for (int64_t base = (int64_t)blockIdx.x * RZ_DECODE_SEGS; base < n_segments;
-       base += (int64_t)gridDim.x * RZ_DECODE_SEGS) {
-    __syncthreads();  // the last round's LDS readers are done
-    uint32_t staged = 0;  // bit t: segment base + t is coded and in LDS
-#pragma unroll
-    for (int t = 0; t < RZ_DECODE_SEGS; ++t) {
-      const int seg = (int)base + t;
-      if (seg >= n_segments) break;
-      const RzSeg g = RZ_SEG(seg);
-      if (g.raw) {
-        wave_copy(g.sp, g.d, g.L, lane);
-      } else if (!g.coded) {
-        if (lane == 0) atomicMin(status, seg + 1);
-      } else {
-        order32[t][lane] = reinterpret_cast<const uint32_t*>(orders + (int64_t)g.blk * 256)[lane];
-        stage_in(g.sp, g.slen, in32[t], lane);
-        staged |= 1u << t;
-      }
-    }
+  for (int64_t s = blockIdx.x; s < n_segments; s += gridDim.x) {
+    __syncthreads();  // the last segment's LDS readers are done
+    const int seg = (int)s;
+    RankSeg g;
+    if (!rank_seg<RZ_ES_MASK, RZ_HI_FIXED>(g, seg, comp, comp_offs, dst_offs, seg_lens, seg_raw,
+                                           seg_blk, blk_es, dst, status, lane))
+      continue;
+    table_in(orders, g.blk, order32, lane);
+    const int mis = stage_in(g.sp, g.slen, in32, lane);
     __syncthreads();
 
-    // the 16 lanes of a segment check k and the end table together: only a
-    // sound table keeps every sub-stream inside the staged bytes
-    const bool walks = mine < RZ_DECODE_SEGS && ((staged >> mine) & 1u);
+    // the 16 walking lanes check k and the end table together: only a sound
+    // table keeps every sub-stream inside the staged bytes
+    const int hi_at = mis + g.lo;
     bool bad = false;
-    int k = 0, e0 = 0, e1 = 0, hi_at = 0;
-    RzSeg g = {};
-    const uint8_t* in = reinterpret_cast<const uint8_t*>(in32[walks ? mine : 0]);
+    int k = 0, e0 = 0, e1 = 0;
     if (walks) {
-      g = RZ_SEG((int)base + mine);
-      hi_at = (int)(reinterpret_cast<uintptr_t>(g.sp) & 3) + g.lo;
       k = in[pad(hi_at)];
       e1 = in[pad(hi_at + 1 + 2 * sub)] | (in[pad(hi_at + 2 + 2 * sub)] << 8);
       if (sub) e0 = in[pad(hi_at - 1 + 2 * sub)] | (in[pad(hi_at + 2 * sub)] << 8);
       bad = k > 7 || e0 > e1 || (sub == RZ_SUBS - 1 && g.lo + RZ_HI_FIXED + e1 != g.slen);
     }
-    uint64_t bad_lanes = __ballot(bad);
-    const bool sound = walks && ((bad_lanes >> (mine * RZ_GROUP)) & 0xFFFFu) == 0;
+    const bool sound = __ballot(walks && bad) == 0;
 
-    if (sound) {
-      const uint32_t* w32 = in32[mine];
-      const uint8_t* order = reinterpret_cast<const uint8_t*>(order32[mine]);
-      uint8_t* outb = reinterpret_cast<uint8_t*>(out32[mine]);
+    if (walks && sound) {
       const int per = (g.m + RZ_SUBS - 1) / RZ_SUBS;
       const int count = min(max(g.m - sub * per, 0), per);
       const int S = hi_at + RZ_HI_FIXED + e0;  // the sub-stream's first staged byte
@@ -338,13 +257,13 @@ extern "C" __global__ __launch_bounds__(WAVE) void ricez_decode_kernel(
       const uint32_t low_mask = (1u << k) - 1;
       int dw = S >> 2;
       const int sh = 8 * (S & 3);
-      uint64_t w = (uint64_t)w32[dw + (dw >> 4)] >> sh;  // `have` bits, zeros above them
+      uint64_t w = (uint64_t)in32[dw + (dw >> 4)] >> sh;  // `have` bits, zeros above them
       int have = 32 - sh, pos = 0;
       int o = sub * per * g.es + g.es - 1;
       for (int j = 0; j < count; ++j) {
         if (have < 32) {
           dw = min(dw + 1, RZ_MAX_DW);
-          w |= (uint64_t)w32[dw + (dw >> 4)] << have;
+          w |= (uint64_t)in32[dw + (dw >> 4)] << have;
           have += 32;
         }
         const int q = __builtin_ctzll(~w | (1ull << RZ_Q_ESC));
@@ -370,71 +289,32 @@ extern "C" __global__ __launch_bounds__(WAVE) void ricez_decode_kernel(
       bad = bad || ((pos + 7) >> 3) != e1 - e0 ||
             ((pos & 7) && ((uint32_t)w & ((1u << (8 - (pos & 7))) - 1)) != 0);
     }
-    bad_lanes |= __ballot(bad);
+    if (__ballot(walks && bad)) { malformed(status, seg, lane); continue; }
 
     // all 64 lanes: the low bytes between the top bytes, then the copy out
-#pragma unroll
-    for (int t = 0; t < RZ_DECODE_SEGS; ++t) {
-      if (!((staged >> t) & 1u)) continue;
-      const int seg = (int)base + t;
-      if ((bad_lanes >> (t * RZ_GROUP)) & 0xFFFFu) {
-        if (lane == 0) atomicMin(status, seg + 1);  // the FIRST malformed one
-        staged &= ~(1u << t);
-        continue;
-      }
-      const RzSeg f = RZ_SEG(seg);
-      const uint8_t* from = reinterpret_cast<const uint8_t*>(in32[t]);
-      uint8_t* outb = reinterpret_cast<uint8_t*>(out32[t]);
-      const int mis = (int)(reinterpret_cast<uintptr_t>(f.sp) & 3);
-      for (int o = lane; o < f.lo; o += WAVE) {
-        const int i = f.es == 2 ? o : o / 3;
-        outb[i * f.es + (o - i * (f.es - 1))] = from[pad(mis + o)];
-      }
-    }
+    low_bytes_in(in, mis, g.es, g.lo, outb, lane);
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < RZ_DECODE_SEGS; ++t) {
-      if (!((staged >> t) & 1u)) continue;
-      const RzSeg f = RZ_SEG((int)base + t);
-      lds_to_global(reinterpret_cast<const uint8_t*>(out32[t]), f.d, f.L, lane);
-    }
+    lds_to_global(outb, g.d, g.L, lane);
   }
-#undef RZ_SEG
 }
 
 // ---------------------------------------------------------------------------
 // host entry points: the table ABI of ma_fpz_encode and ma_fpz_decode
 // ---------------------------------------------------------------------------
 
-// max_segs: the largest segment count of any block (bounds the grid).
 extern "C" int ma_ricez_encode(const void* src, const void* blk_src_off,
                                const void* blk_raw_len, const void* blk_first_seg,
                                const void* rank_of, int es, void* stride_buf, int out_stride,
                                void* comp_lens, int n_blocks, long max_segs, void* stream) {
-  if (n_blocks <= 0 || max_segs <= 0) return 0;
-  if (es != 1 && es != 2 && es != 4) return (int)hipErrorInvalidValue;
-  const int gx = (int)(max_segs < 16384 ? max_segs : 16384);
-  return launch_chunked(n_blocks, [&](int base, int ny) {
-    hipLaunchKernelGGL(ricez_encode_kernel, dim3(gx, ny), dim3(WAVE), 0, (hipStream_t)stream,
-                       (const uint8_t*)src, (const int64_t*)blk_src_off,
-                       (const int64_t*)blk_raw_len, (const int32_t*)blk_first_seg,
-                       (const uint8_t*)rank_of, es, (uint8_t*)stride_buf, out_stride,
-                       (int32_t*)comp_lens, base);
-  });
+  return launch_rank_encode(ricez_encode_kernel, es == 1 || es == 2 || es == 4, n_blocks,
+                            max_segs, stream, src, blk_src_off, blk_raw_len, blk_first_seg,
+                            rank_of, es, stride_buf, out_stride, comp_lens);
 }
 
 extern "C" int ma_ricez_decode(const void* comp, const void* comp_offs, const void* dst_offs,
                                const void* seg_lens, const void* seg_raw, const void* seg_blk,
                                const void* orders, const void* blk_es, void* dst, void* status,
                                int n_segments, void* stream) {
-  if (n_segments <= 0) return 0;
-  const int rounds = (n_segments + RZ_DECODE_SEGS - 1) / RZ_DECODE_SEGS;
-  const int gx = rounds < (1 << 20) ? rounds : (1 << 20);
-  hipLaunchKernelGGL(ricez_decode_kernel, dim3(gx), dim3(WAVE), 0, (hipStream_t)stream,
-                     (const uint8_t*)comp, (const int64_t*)comp_offs,
-                     (const int64_t*)dst_offs, (const int32_t*)seg_lens,
-                     (const int32_t*)seg_raw, (const int32_t*)seg_blk,
-                     (const uint8_t*)orders, (const uint8_t*)blk_es, (uint8_t*)dst,
-                     (int32_t*)status, n_segments);
-  return (int)hipGetLastError();
+  return launch_rank_decode(ricez_decode_kernel, n_segments, stream, comp, comp_offs, dst_offs,
+                            seg_lens, seg_raw, seg_blk, orders, blk_es, dst, status);
 }
